@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — ISDF build + 1x get_jk on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--no-cpu-baseline] [--dump-outputs DIR]
 
 One "step" = ISDF.build() (collocation, interpolation-point selection, fit, Coulomb W) followed by
 one get_jk() on a synthetic density matrix; the cell tables and the density matrix are already
@@ -28,6 +28,7 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # AMD datasheet, MI355X FP64 matrix (the guide's 
                                # best rocBLAS dgemm measured on the box: 73.8 (profiles/r01_probe_*.log)
 PMC_FILE = 'r03_pmc_bench_cfg3_spectral_fetch_write.json'
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 
 def parse_args():
@@ -58,7 +59,40 @@ def parse_args():
                          "by plane-wave quadrature of the AO values); Gamma-point workloads, one GPU")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--stage-report', default=None, help='write the per-kernel table to this file')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (vj, vk) as DIR/<name>.npy in float64 '
+                         '(complex arrays as a trailing axis of 2: real, imaginary); above %d MB in all, a fixed seeded sample of '
+                         'each array (flat indices in DIR/<name>_index.npy)' % (DUMP_LIMIT_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array of ``arrays`` (name -> array) to outdir/<name>.npy as float64, complex values as a trailing axis of
+    2.  When the arrays hold more than ``limit`` bytes in all, each keeps the same share of its elements, drawn by a
+    generator of fixed seed (so two runs of the same command write the same positions) and stored with their flat indices
+    in outdir/<name>_index.npy.  Returns {name: shape written}."""
+    os.makedirs(outdir, exist_ok=True)
+    parts = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        parts[name] = np.ascontiguousarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in parts.values())
+    written = {}
+    for name, a in parts.items():
+        if total > limit:
+            # the index file counts against the limit as well (values and indices take 8 bytes each); 64 KB left for headers
+            keep = max(1, int(a.size * ((limit - (64 << 10)) // 2) // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(outdir, name + '_index.npy'), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def cpu_baseline(cell, c_isdf, gpu_stage_sizes):
@@ -372,6 +406,9 @@ def main():
     per_rank = comm.all_gather_object(mine) if world > 1 else [mine]
 
     if rank == 0:
+        if args.dump_outputs:
+            written = dump_outputs(args.dump_outputs, {'vj': vj, 'vk': vk})
+            print('[bench] last timed step\'s outputs written to %s: %s' % (args.dump_outputs, written), file=sys.stderr, flush=True)
         prof = be.prof_results()
         rows = []
         for name, r in prof.items():

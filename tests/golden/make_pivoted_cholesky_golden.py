@@ -1,8 +1,8 @@
 """Generate golden pivot lists from the REFERENCE's pivoted Cholesky
-(/root/reference/pyscf/lib/scipy_helper.py:71-110, loaded standalone by path — it needs only numpy).
+(pyscf/lib/scipy_helper.py:71-110 of a PySCF source tree, loaded standalone by path — it needs only numpy).
 
-Run in the build container only (the reference does not exist on the GPU box):
-    python tests/golden/make_pivoted_cholesky_golden.py
+Run where a PySCF source tree is at hand (the tests only read the JSON this writes):
+    python tests/golden/make_pivoted_cholesky_golden.py PATH_TO_PYSCF_SOURCE_TREE
 Writes tests/golden/pivoted_cholesky_golden.json: for each case the seed/shape that regenerates the
 input AO-like matrix and the pivots + rank + diagonal of the factor the reference returns on the
 explicitly formed pair-density Gram matrix A = (ao^T ao)^2.
@@ -10,10 +10,13 @@ explicitly formed pair-density Gram matrix A = (ao^T ao)^2.
 import importlib.util
 import json
 import os
+import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-spec = importlib.util.spec_from_file_location('ref_scipy_helper', '/root/reference/pyscf/lib/scipy_helper.py')
+if len(sys.argv) != 2:
+    sys.exit(__doc__)
+spec = importlib.util.spec_from_file_location('ref_scipy_helper', os.path.join(sys.argv[1], 'pyscf', 'lib', 'scipy_helper.py'))
 ref = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(ref)
 
