@@ -501,6 +501,18 @@ int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const double* d_
  *                               planes, wstride apart); rho <= 1e-14 gives zero
  *   isdf_lda_exchange_fxc:      its second derivative f = d2(rho exc)/d rho2 (the LDA kernel of multigrid.py:1259-1452's response
  *                               functions; densities <= 1e-24 give zero)
+ *   isdf_lda_vwn_fxc_add:       fxc += d2(rho eps_c)/d rho2 of the VWN5 correlation of isdf_lda_vwn_add (closed shell; densities
+ *                               <= 1e-24 add nothing)
+ *   isdf_gga_b88_fxc:           Becke-88 response, fused: from rho0 and grad rho0 (four planes, r0stride apart) the kernel fxc (4, 4)
+ *                               of eval_xc_eff (fxc[0][0] = v2rho2, fxc[0][i] = 2 v2rhosigma d_i rho, fxc[i][j] = 4 v2sigma2 d_i rho
+ *                               d_j rho + 2 vsigma delta_ij) is made once per point and applied to nset response 4-vectors:
+ *                               wv[n][y] = sum_x rho1[n][x] fxc[x][y], plane (x, n) of rho1 at x * r1xstride + n * r1nstride, of wv
+ *                               at y * wxstride + n * wnstride.  d_fxc (NULL: skipped) receives the 10 unique components
+ *                               (00 01 02 03 11 12 13 22 23 33), fstride apart; nset may be 0 when d_fxc is given.  rho <= 1e-14
+ *                               gives zero
+ *   isdf_xc_fxc_apply:          wv[n][y] (+)= sum_x rho1[n][x] fxc[x][y] for a caller's kernel, nx = 1 or 4, fxc[x][y] at
+ *                               x * fxstride + y * fystride (einsum('nxg,xyg->nyg') of multigrid.py:1302; one spin block of the
+ *                               (2, nx, 2, nx, G) open-shell kernel per call, accumulate = 1 adds the next block)
  *   isdf_dot:                   *result (host) = sum x_i y_i, d_y NULL: sum x_i; fixed summation order; synchronises */
 int isdf_uniform_grid(isdf_handle h, const int32_t mesh[3], const double a[9], double* d_coords_soa);
 int isdf_rho_pair(isdf_handle h, const double* d_aoA, int nA, const double* d_aoB, int nB, int64_t ng, int64_t ld,
@@ -515,6 +527,11 @@ int isdf_lda_vwn_add(isdf_handle h, const double* d_rho, int64_t n, double* d_ex
 int isdf_gga_b88(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double* d_exc,
                  double* d_vrho, double* d_w, int64_t wstride);
 int isdf_lda_exchange_fxc(isdf_handle h, const double* d_rho, int64_t n, double* d_fxc);
+int isdf_lda_vwn_fxc_add(isdf_handle h, const double* d_rho, int64_t n, double* d_fxc);
+int isdf_gga_b88_fxc(isdf_handle h, const double* d_rho0, int64_t r0stride, int64_t n, const double* d_rho1, int64_t r1xstride,
+                     int64_t r1nstride, int nset, double* d_wv, int64_t wxstride, int64_t wnstride, double* d_fxc, int64_t fstride);
+int isdf_xc_fxc_apply(isdf_handle h, int nx, const double* d_fxc, int64_t fxstride, int64_t fystride, int64_t n, const double* d_rho1,
+                      int64_t r1xstride, int64_t r1nstride, int nset, double* d_wv, int64_t wxstride, int64_t wnstride, int accumulate);
 int isdf_dot(isdf_handle h, const double* d_x, const double* d_y, int64_t n, double* result);
 
 /* Dense helper behind S5/S6 (exposed for tests and micro-benchmarks):

@@ -558,6 +558,37 @@ class HipBackend:
         assert rho.is_contiguous() and fxc.is_contiguous() and rho.numel() == fxc.numel()
         self.handle.call('isdf_lda_exchange_fxc', self._p(rho), rho.numel(), self._p(fxc))
 
+    def lda_vwn_fxc_add(self, rho, fxc):
+        """fxc += d2(rho eps_c)/d rho2 (VWN5 correlation, closed shell)."""
+        self._stream()
+        assert rho.is_contiguous() and fxc.is_contiguous() and rho.numel() == fxc.numel()
+        self.handle.call('isdf_lda_vwn_fxc_add', self._p(rho), rho.numel(), self._p(fxc))
+
+    def gga_b88_fxc(self, rho0, rho1, wv, fxc=None):
+        """rho0 (4, G) -> wv (4, nset, G) = sum_x rho1[x, n] fxc[x, y] of the B88 kernel; rho1 / wv may be strided views
+        (points contiguous); fxc (10, G) or None: the kernel's unique components (00 01 02 03 11 12 13 22 23 33)."""
+        self._stream()
+        G = rho0.shape[1]
+        assert rho0.shape[0] == 4 and rho0.stride(1) == 1
+        nset = 0 if rho1 is None else rho1.shape[1]
+        if nset:
+            assert rho1.shape == (4, nset, G) and tuple(wv.shape) == (4, nset, G) and rho1.stride(2) == 1 and wv.stride(2) == 1
+        if fxc is not None:
+            assert fxc.shape == (10, G) and fxc.stride(1) == 1
+        self.handle.call('isdf_gga_b88_fxc', self._p(rho0), rho0.stride(0), G,
+                         self._p(rho1) if nset else _vp(0), rho1.stride(0) if nset else 0, rho1.stride(1) if nset else 0, nset,
+                         self._p(wv) if nset else _vp(0), wv.stride(0) if nset else 0, wv.stride(1) if nset else 0,
+                         self._p(fxc) if fxc is not None else _vp(0), fxc.stride(0) if fxc is not None else 0)
+
+    def xc_fxc_apply(self, fxc, rho1, wv, accumulate=False):
+        """wv (nx, nset, G) (+)= einsum('xng,xyg->yng', rho1, fxc) with fxc (nx, nx, G); all three may be strided views."""
+        self._stream()
+        nx, nset, G = rho1.shape
+        assert nx in (1, 4) and fxc.shape == (nx, nx, G) and tuple(wv.shape) == (nx, nset, G)
+        assert fxc.stride(2) == 1 and rho1.stride(2) == 1 and wv.stride(2) == 1
+        self.handle.call('isdf_xc_fxc_apply', nx, self._p(fxc), fxc.stride(0), fxc.stride(1), G, self._p(rho1), rho1.stride(0),
+                         rho1.stride(1), nset, self._p(wv), wv.stride(0), wv.stride(1), int(bool(accumulate)))
+
     def dot(self, x, y=None):
         self._stream()
         assert x.is_contiguous() and (y is None or (y.is_contiguous() and y.numel() == x.numel()))

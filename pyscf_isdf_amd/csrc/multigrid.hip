@@ -215,6 +215,119 @@ __global__ void lda_exchange_fxc_kernel(const double* __restrict__ rho, int64_t 
   fxc[i] = f;
 }
 
+// d2(rho eps_c)/d rho2 of the VWN5 correlation of lda_vwn_add_kernel: with v_c = eps_c - (x/6) eps_c'(x) and dx/drho = -x/(6 rho),
+// f_c = -x (5 eps_c' - x eps_c'') / (36 rho); ADDED to fxc (the exchange part comes from lda_exchange_fxc_kernel)
+__global__ void lda_vwn_fxc_add_kernel(const double* __restrict__ rho, int64_t n, double* __restrict__ fxc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = rho[i];
+  if (!(r > 1e-24)) return;
+  const double A = 0.0310907, b = 3.72744, c = 12.9352, x0 = -0.10498;
+  const double rs = cbrt(3.0 / (4.0 * 3.14159265358979323846 * r));
+  const double x = sqrt(rs);
+  const double X = x * x + b * x + c, X0 = x0 * x0 + b * x0 + c;
+  const double Q = sqrt(4.0 * c - b * b);
+  const double t = 2.0 * x + b;
+  const double den = Q * Q + t * t;
+  const double dec = A * (2.0 / x - t / X - 4.0 * b / den - b * x0 / X0 * (2.0 / (x - x0) - t / X - 4.0 * (b + 2.0 * x0) / den));
+  const double dtX = (2.0 * X - t * t) / (X * X);                          // d/dx (2x + b) / X
+  const double d2ec = A * (-2.0 / (x * x) - dtX + 16.0 * b * t / (den * den)
+                           - b * x0 / X0 * (-2.0 / ((x - x0) * (x - x0)) - dtX + 16.0 * (b + 2.0 * x0) * t / (den * den)));
+  fxc[i] += -x * (5.0 * dec - x * d2ec) / (36.0 * r);
+}
+
+// Becke-88 second derivative of the closed-shell energy density e(rho, grad rho) = 2 f(rho/2, |grad rho|/2) of gga_b88_kernel, in
+// the layout of eval_xc_eff (spin 0, (4, 4) per point over (rho, d_x rho, d_y rho, d_z rho)):
+//   fxc[0][0] = v2rho2 = (2/9) rho_s^(-2/3) (G - x G' + 4 x^2 G''),
+//   fxc[0][i] = 2 v2rhosigma d_i rho = -G'' / (3 rho_s^(7/3)) d_i rho,
+//   fxc[i][j] = 4 v2sigma2 d_i rho d_j rho + 2 vsigma delta_ij = (G'' - G'/x) / x^2 / (8 rho_s^4) d_i rho d_j rho
+//               + G'/x / (2 rho_s^(4/3)) delta_ij.
+// With u = x^2 / D, D = 1 + 6 beta x asinh x: G' = -beta u', G'' = -beta u'' and (G'' - G'/x) / x^2 = -beta (2 D'^2 - D D'' - 3 D D'/x)
+// / D^3, where D'/x = 6 beta (asinh(x)/x + 1/sqrt(1 + x^2)) - every term finite at x = 0 once asinh(x)/x is taken from its series
+// below x = 1e-3 (the next term, 5 x^6 / 112, is below the rounding there).  rho <= 1e-14 gives zero, as the potential.
+// Output: the 10 unique components, row-major upper triangle (00 01 02 03 11 12 13 22 23 33).
+__device__ inline void b88_fxc_point(double r, double gx, double gy, double gz, double f[10]) {
+  for (int k = 0; k < 10; ++k) f[k] = 0.0;
+  if (!(r > 1e-14)) return;
+  const double beta = 0.0042;
+  const double cx = 1.5 * cbrt(3.0 / (4.0 * 3.14159265358979323846));
+  const double rs = 0.5 * r;
+  const double r13 = cbrt(rs), r43 = rs * r13;
+  const double x = 0.5 * sqrt(gx * gx + gy * gy + gz * gz) / r43;
+  const double x2 = x * x;
+  const double as = asinh(x);
+  const double s = sqrt(1.0 + x2);
+  const double ash_x = x < 1e-3 ? 1.0 - x2 / 6.0 + 0.075 * x2 * x2 : as / x;
+  const double D = 1.0 + 6.0 * beta * x * as;
+  const double Dp = 6.0 * beta * (as + x / s);
+  const double Dpp = 6.0 * beta * (2.0 + x2) / (s * s * s);
+  const double Dp_x = 6.0 * beta * (ash_x + 1.0 / s);
+  const double D3 = D * D * D;
+  const double Gx = -cx - beta * x2 / D;
+  const double Gp_x = -beta * (2.0 * D - x * Dp) / (D * D);
+  const double Gpp = -beta * ((2.0 * D - x2 * Dpp) * D - 2.0 * x * Dp * (2.0 * D - x * Dp)) / D3;
+  const double H = -beta * (2.0 * Dp * Dp - D * Dpp - 3.0 * D * Dp_x) / D3;
+  const double f00 = (2.0 / 9.0) * (Gx - x2 * Gp_x + 4.0 * x2 * Gpp) / (r13 * r13);
+  const double c01 = -Gpp / (3.0 * rs * r43);
+  const double vs2 = Gp_x / (2.0 * r43);
+  const double s2 = H / (8.0 * rs * rs * rs * rs);
+  f[0] = f00;
+  f[1] = c01 * gx; f[2] = c01 * gy; f[3] = c01 * gz;
+  f[4] = s2 * gx * gx + vs2; f[5] = s2 * gx * gy; f[6] = s2 * gx * gz;
+  f[7] = s2 * gy * gy + vs2; f[8] = s2 * gy * gz;
+  f[9] = s2 * gz * gz + vs2;
+}
+
+// index of (x, y) in the 10-component upper triangle
+__device__ inline int sym4(int x, int y) {
+  const int a = x < y ? x : y, b = x < y ? y : x;
+  return a * 4 - a * (a - 1) / 2 + (b - a);
+}
+
+// wv[n][y] = sum_x rho1[n][x] fxc[x][y] with the B88 kernel of rho0 (4 planes, r0s apart): the kernel is made once per point and
+// applied to all nset response 4-vectors (plane (x, n) at x * r1x + n * r1n, output at y * wx + n * wn); fout (optional): the 10
+// unique components, fs apart
+__global__ void gga_b88_fxc_kernel(const double* __restrict__ rho0, int64_t r0s, int64_t n, const double* __restrict__ rho1,
+                                   int64_t r1x, int64_t r1n, int nset, double* __restrict__ wv, int64_t wx, int64_t wn,
+                                   double* __restrict__ fout, int64_t fs) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double f[10];
+  b88_fxc_point(rho0[i], rho0[r0s + i], rho0[2 * r0s + i], rho0[3 * r0s + i], f);
+  if (fout)
+    for (int k = 0; k < 10; ++k) fout[k * fs + i] = f[k];
+  for (int m = 0; m < nset; ++m) {
+    double r1[4];
+    for (int x = 0; x < 4; ++x) r1[x] = rho1[x * r1x + m * r1n + i];
+    for (int y = 0; y < 4; ++y) {
+      double acc = 0.0;
+      for (int x = 0; x < 4; ++x) acc = fma(r1[x], f[sym4(x, y)], acc);
+      wv[y * wx + m * wn + i] = acc;
+    }
+  }
+}
+
+// wv[n][y] (+)= sum_x rho1[n][x] fxc[x][y] for a caller's kernel (x, y < NX; fxc[x][y] at x * fx + y * fy)
+template <int NX>
+__global__ void xc_fxc_apply_kernel(const double* __restrict__ fxc, int64_t fx, int64_t fy, int64_t n, const double* __restrict__ rho1,
+                                    int64_t r1x, int64_t r1n, int nset, double* __restrict__ wv, int64_t wx, int64_t wn, int accumulate) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double f[NX][NX];
+  for (int x = 0; x < NX; ++x)
+    for (int y = 0; y < NX; ++y) f[x][y] = fxc[x * fx + y * fy + i];
+  for (int m = 0; m < nset; ++m) {
+    double r1[NX];
+    for (int x = 0; x < NX; ++x) r1[x] = rho1[x * r1x + m * r1n + i];
+    for (int y = 0; y < NX; ++y) {
+      double acc = 0.0;
+      for (int x = 0; x < NX; ++x) acc = fma(r1[x], f[x][y], acc);
+      double* p = wv + y * wx + m * wn + i;
+      *p = accumulate ? *p + acc : acc;
+    }
+  }
+}
+
 // two-stage deterministic reduction: partial[b] = sum over block b's strided elements of x (* y)
 __global__ void dot_partial_kernel(const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ partial) {
   __shared__ double sh[256];
@@ -384,6 +497,45 @@ extern "C" int isdf_lda_exchange_fxc(isdf_handle h, const double* d_rho, int64_t
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_rho && d_fxc && n > 0);
   hipLaunchKernelGGL(lda_exchange_fxc_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, n, d_fxc);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_lda_vwn_fxc_add(isdf_handle h, const double* d_rho, int64_t n, double* d_fxc) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_rho && d_fxc && n > 0);
+  hipLaunchKernelGGL(lda_vwn_fxc_add_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, n, d_fxc);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_gga_b88_fxc(isdf_handle h, const double* d_rho0, int64_t r0stride, int64_t n, const double* d_rho1,
+                                int64_t r1xstride, int64_t r1nstride, int nset, double* d_wv, int64_t wxstride, int64_t wnstride,
+                                double* d_fxc, int64_t fstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_rho0 && n > 0 && r0stride >= n && nset >= 0 && (nset > 0 || d_fxc));
+  ARG_CHECK(h, nset == 0 || (d_rho1 && d_wv && r1xstride > 0 && r1nstride > 0 && wxstride > 0 && wnstride > 0));
+  ARG_CHECK(h, !d_fxc || fstride >= n);
+  ProfScope ps(h, "gga_b88_fxc_kernel[byte]", 8.0 * (double)n * (4.0 + 8.0 * nset + (d_fxc ? 10.0 : 0.0)));
+  hipLaunchKernelGGL(gga_b88_fxc_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho0, r0stride, n, d_rho1,
+                     r1xstride, r1nstride, nset, d_wv, wxstride, wnstride, d_fxc, fstride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_xc_fxc_apply(isdf_handle h, int nx, const double* d_fxc, int64_t fxstride, int64_t fystride, int64_t n,
+                                 const double* d_rho1, int64_t r1xstride, int64_t r1nstride, int nset, double* d_wv, int64_t wxstride,
+                                 int64_t wnstride, int accumulate) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, (nx == 1 || nx == 4) && d_fxc && d_rho1 && d_wv && n > 0 && nset > 0);
+  ARG_CHECK(h, (nx == 1 || (fxstride > 0 && fystride > 0)) && r1nstride > 0 && wnstride > 0 && (nx == 1 || (r1xstride > 0 && wxstride > 0)));
+  const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+  if (nx == 1)
+    hipLaunchKernelGGL(xc_fxc_apply_kernel<1>, grid, block, 0, h->stream, d_fxc, fxstride, fystride, n, d_rho1, r1xstride, r1nstride,
+                       nset, d_wv, wxstride, wnstride, accumulate);
+  else
+    hipLaunchKernelGGL(xc_fxc_apply_kernel<4>, grid, block, 0, h->stream, d_fxc, fxstride, fystride, n, d_rho1, r1xstride, r1nstride,
+                       nset, d_wv, wxstride, wnstride, accumulate);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

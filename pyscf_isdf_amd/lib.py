@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libmi355_isdf.so')
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _lib = None
 
@@ -102,6 +102,9 @@ SIGNATURES = {
     'isdf_lda_vwn_add': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     'isdf_gga_b88': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64]),
     'isdf_lda_exchange_fxc': (c_int, [c_vp, c_vp, c_i64, c_vp]),
+    'isdf_lda_vwn_fxc_add': (c_int, [c_vp, c_vp, c_i64, c_vp]),
+    'isdf_gga_b88_fxc': (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_i64, c_vp, c_i64]),
+    'isdf_xc_fxc_apply': (c_int, [c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_i64, c_int]),
     'isdf_dot': (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
     'isdf_gemm_nt': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i64]),
     'isdf_get_k_exact': (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

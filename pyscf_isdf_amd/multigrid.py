@@ -26,7 +26,8 @@ Everything numerical runs in libmi355_isdf.so (multigrid.hip, eval_ao.hip, gemm_
 scatters the small level matrices into J on the host.
 
 Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc,
-cache_xc_kernel1, multi_grids_tasks, multigrid_fftdf - the names of pyscf/pbc/dft/multigrid/__init__.py.
+cache_xc_kernel1, _gen_rhf_response, _gen_uhf_response, multi_grids_tasks, multigrid_fftdf - the names of
+pyscf/pbc/dft/multigrid/__init__.py and multigrid.py.
 
 K is the ISDF exchange of the parent class (``MultiGridFFTDF(ISDF)``): hybrid functionals get J/XC from here and K from the
 interpolation, which is the pairing SURVEY section 8 f-3 names.  XC: the Slater exchange ('lda,') and Becke's 1988 exchange
@@ -922,7 +923,7 @@ def nr_uks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=Fa
     return nelec, excsum, TaggedArray(veff, ecoul=ecoul, exc=excsum, vj=vj, vk=None)
 
 
-# ---- linear response of the LDA potential (TDDFT / stability / Hessians), multigrid.py:1259-1500 ---------------------------
+# ---- linear response of the XC potential (TDDFT / stability / Hessians), multigrid.py:1259-1550 ---------------------------
 def _density_passes(mydf, dm_in, kpts):
     """What the response functions share: the spectra of the (real) densities a stack of matrices stands for, each with its
     factor (Gamma: one pass; k-points: Hermitian and, if present, anti-Hermitian part), an integrator and the result shape."""
@@ -950,8 +951,9 @@ def _ground_density(mydf, dm0, kpts, scale=1.0):
     return _real_space(mydf, passes[0][1], scale / mydf.cell.vol)
 
 
-def _response(mydf, dms, kpts, kernel_rows, with_j, total_j=False, w_scale=1.0):
-    """veff[n] = matrix of  w_scale * kernel_rows[n] * rho1[n]  (+ Hartree potential of rho1[n], or of the pair's sum with total_j)."""
+def _response(mydf, dms, kpts, kernel_rows, with_j, total_j=False, w_scale=1.0, contract=None):
+    """veff[n] = matrix of  w_scale * kernel_rows[n] * rho1[n]  (+ Hartree potential of rho1[n], or of the pair's sum with total_j);
+    ``contract`` (rho1 (1, nset, G) -> w (1, nset, G)) replaces the row product for a caller-supplied kernel."""
     be, cell = mydf.backend, mydf.cell
     mesh = np.asarray(mydf.mesh, dtype=np.int32)
     weight = cell.vol / int(np.prod(mesh))
@@ -959,17 +961,15 @@ def _response(mydf, dms, kpts, kernel_rows, with_j, total_j=False, w_scale=1.0):
     veff = 0.0
     for fac, spec in passes:
         w = _real_space(mydf, spec, 1.0 / cell.vol)                          # rho1 (nset, G)
-        for n in range(nset):
-            be.hadamard_rows(w[n:n + 1], kernel_rows[n:n + 1])
+        if contract is not None:
+            w = contract(w[None])[0]
+        else:
+            for n in range(nset):
+                be.hadamard_rows(w[n:n + 1], kernel_rows[n:n + 1])
         if with_j:
             be.mg_coulomb_kernel(spec, mesh, cell.lattice_vectors())
             if total_j:                                                      # both spins feel the Hartree potential of the sum
-                vH = _real_space(mydf, spec, 1.0 / cell.vol)
-                swapped = be.empty(tuple(vH.shape))
-                half = nset // 2
-                swapped[:half].copy_(vH[half:])
-                swapped[half:].copy_(vH[:half])
-                be.mg_embed_density(swapped, mesh, weight, spec, mesh, accumulate=True)
+                _add_partner_hartree(mydf, spec, nset)
         else:
             spec.zero_()
         be.mg_embed_density(w, mesh, weight * w_scale, spec, mesh, accumulate=True)
@@ -977,13 +977,42 @@ def _response(mydf, dms, kpts, kernel_rows, with_j, total_j=False, w_scale=1.0):
     return np.asarray(veff)
 
 
-def _check_lda(xc_code):
-    if not _is_slater(xc_code):
-        raise NotImplementedError("xc=%r: only the Slater exchange ('lda,') is implemented (no libxc in this tree)" % (xc_code,))
+def _add_partner_hartree(mydf, spec, nset):
+    """spec rows hold the Hartree potentials of (alpha responses | beta responses): add to each the one of its partner spin."""
+    be, cell = mydf.backend, mydf.cell
+    mesh = np.asarray(mydf.mesh, dtype=np.int32)
+    vH = _real_space(mydf, spec, 1.0 / cell.vol)
+    swapped = be.empty(tuple(vH.shape))
+    half = nset // 2
+    swapped[:half].copy_(vH[half:])
+    swapped[half:].copy_(vH[:half])
+    be.mg_embed_density(swapped, mesh, cell.vol / int(np.prod(mesh)), spec, mesh, accumulate=True)
 
 
-def _kernel_rows(mydf, rho0_dev, fxc, nrows):
-    """Device rows f[n] = f_x(density row) (or the caller's fxc), one per response density (ground-state rows repeated)."""
+def _response_kind(xc_code, open_shell=False):
+    """'lda' / 'vwn' / 'b88' for the response functions; open_shell: the spin-resolved kernel is needed (nr_uks_fxc, the triplet,
+    cache_xc_kernel1(spin=1)) - for 'lda,vwn' that is the spin-polarised VWN, which is not implemented."""
+    kind = _xc_kind(xc_code)
+    if kind is None:
+        raise NotImplementedError("xc=%r: the response is implemented for 'lda,', 'lda,vwn' and 'b88,' (no libxc in this tree)"
+                                  % (xc_code,))
+    if kind == 'lda' and _has_vwn(xc_code):
+        if open_shell:
+            raise NotImplementedError("xc=%r: the spin-polarised VWN correlation is not implemented (open-shell and triplet "
+                                      "response; the closed-shell nr_rks_fxc and the singlet are)" % (xc_code,))
+        return 'vwn'
+    return kind
+
+
+def _nset_of(mydf, dms, kpts):
+    nao = mydf.cell.nao_nr()
+    nk = 1 if kpts is None or mydf._is_gamma(kpts) else len(np.asarray(kpts).reshape(-1, 3))
+    return int(np.asarray(dms).size // (nk * nao * nao))
+
+
+def _kernel_rows(mydf, rho0_dev, fxc, nrows, vwn=False):
+    """Device rows f[n] = f_x(density row) (+ f_c of VWN5) (or the caller's fxc), one per response density (ground-state rows
+    repeated)."""
     be = mydf.backend
     if fxc is not None:
         f = be.to_device(np.ascontiguousarray(np.asarray(fxc, dtype=np.float64).reshape(-1, rho0_dev.shape[1])))
@@ -991,6 +1020,8 @@ def _kernel_rows(mydf, rho0_dev, fxc, nrows):
         f = be.empty(tuple(rho0_dev.shape))
         for i in range(rho0_dev.shape[0]):
             be.lda_exchange_fxc(rho0_dev[i], f[i])
+            if vwn:
+                be.lda_vwn_fxc_add(rho0_dev[i], f[i])
     reps = nrows // f.shape[0]
     if reps <= 1:
         return f
@@ -1000,20 +1031,158 @@ def _kernel_rows(mydf, rho0_dev, fxc, nrows):
     return out
 
 
-def nr_rks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
-    """Closed-shell response matrix f_xc[rho0] rho1 (+ J[rho1]) of the matrices ``dms`` (multigrid.py:1259-1318), 'lda,'."""
-    _check_lda(xc_code)
+# ---- GGA ('b88,') response: (rho1, grad rho1) from the ladder, the fused kernel isdf_gga_b88_fxc, the GGA integration pass ----------
+def _density_passes_gga(mydf, dm_in, kpts):
+    """_density_passes with gradients: [(factor, spec4 (4, nset, gc))], the GGA integrator and nset."""
+    nao = mydf.cell.nao_nr()
+    dm_in = np.asarray(dm_in)
+    if kpts is None or mydf._is_gamma(kpts):
+        shape, dms = mydf._real_dms(dm_in)
+        return [(1.0, mydf._eval_rhoG_gga(dms))], (lambda sp4: mydf._integrate_gga(sp4).reshape(shape)), dms.shape[0]
+    kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
+    dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
+    passes = [(fac, mydf._eval_rhoG_gga_k(part, kpts)) for fac, part in mydf._hermitian_parts(dms)]
+    return passes, (lambda sp4: mydf._integrate_gga_k(sp4, kpts).reshape(dm_in.shape)), dms.shape[0]
+
+
+def _ground_density_gga(mydf, dm0, kpts, scale=1.0):
+    """scale * (rho, grad rho) of the ground-state matrix (or (alpha, beta) pair) on the dense mesh, device (4, nset, G)."""
+    passes, _, nset = _density_passes_gga(mydf, dm0, kpts)
+    spec4 = passes[0][1]
+    out = mydf.backend.empty((4, nset, int(np.prod(mydf.mesh))))
+    for c in range(4):
+        out[c].copy_(_real_space(mydf, spec4[c], scale / mydf.cell.vol))
+    return out
+
+
+def _response_gga(mydf, dms, kpts, contract, with_j, total_j=False, w_scale=1.0):
+    """veff[n] = GGA matrix of  w_scale * wv[n]  with wv = contract(rho1) (4, nset, G), rho1 = (rho, grad rho) of each response
+    matrix (+ Hartree potential of rho1[n], or of the pair's sum with total_j, on component 0)."""
+    be, cell = mydf.backend, mydf.cell
+    mesh = np.asarray(mydf.mesh, dtype=np.int32)
+    G = int(np.prod(mesh))
+    weight = cell.vol / G
+    passes, integrate, nset = _density_passes_gga(mydf, dms, kpts)
+    veff = 0.0
+    for fac, spec4 in passes:
+        rho1 = be.empty((4, nset, G))
+        for c in range(4):
+            be.mg_restrict_potential(spec4[c], mesh, mesh, 1.0 / cell.vol, rho1[c])
+        wv = contract(rho1)
+        del rho1
+        if with_j:
+            be.mg_coulomb_kernel(spec4[0], mesh, cell.lattice_vectors())
+            if total_j:
+                _add_partner_hartree(mydf, spec4[0], nset)
+        else:
+            spec4[0].zero_()
+        spec4[1:].zero_()
+        for c in range(4):
+            be.mg_embed_density(wv[c], mesh, weight * w_scale, spec4[c], mesh, accumulate=True)
+        veff = veff + fac * integrate(spec4)
+    return np.asarray(veff)
+
+
+def _b88_contract(mydf, rho0):
+    """rho1 (4, nset, G) -> wv of the B88 kernel at rho0 (4, G) (device)."""
+    def contract(rho1):
+        wv = mydf.backend.empty(tuple(rho1.shape))
+        mydf.backend.gga_b88_fxc(rho0, rho1, wv)
+        return wv
+    return contract
+
+
+def _b88_contract_spins(mydf, rho0_2):
+    """Open shell by spin scaling: rows of spin s (the s-th half of rho1) see the kernel at 2 rho_s, rho0_2 (4, 2, G) = (2 rho_s, ...);
+    the factor 2 of f_ss = 2 f(2 rho_s) is the caller's w_scale."""
+    def contract(rho1):
+        be = mydf.backend
+        half = rho1.shape[1] // 2
+        wv = be.empty(tuple(rho1.shape))
+        for sp in range(2):
+            sl = slice(sp * half, (sp + 1) * half)
+            be.gga_b88_fxc(rho0_2[:, sp], rho1[:, sl], wv[:, sl])
+        return wv
+    return contract
+
+
+def _fxc_contract(mydf, fxc):
+    """rho1 (nx, nset, G) -> wv of a caller-supplied closed-shell kernel fxc (nx, nx, G) (isdf_xc_fxc_apply)."""
     be = mydf.backend
+    f = np.asarray(fxc, dtype=np.float64)
+    nx = 1 if f.ndim <= 2 else f.shape[0]
+    f_dev = be.to_device(np.ascontiguousarray(f.reshape(nx, nx, -1)))
+
+    def contract(rho1):
+        wv = be.empty(tuple(rho1.shape))
+        be.xc_fxc_apply(f_dev, rho1, wv)
+        return wv
+    return contract
+
+
+def _fxc_contract_spins(mydf, fxc):
+    """Open-shell kernel fxc (2, nx, 2, nx, G): wv of spin b = sum_a rho1 of spin a through block fxc[a, :, b, :]."""
+    be = mydf.backend
+    f = np.asarray(fxc, dtype=np.float64)
+    nx = f.shape[1]
+    f_dev = be.to_device(np.ascontiguousarray(f.reshape(2, nx, 2, nx, -1)))
+
+    def contract(rho1):
+        half = rho1.shape[1] // 2
+        wv = be.empty(tuple(rho1.shape))
+        for b in range(2):
+            for a in range(2):
+                be.xc_fxc_apply(f_dev[a, :, b], rho1[:, a * half:(a + 1) * half], wv[:, b * half:(b + 1) * half], accumulate=a > 0)
+        return wv
+    return contract
+
+
+def _b88_kernel_host(mydf, rho0):
+    """(vxc (4, G), fxc (4, 4, G)) of B88 at rho0 (4, G) device: the potential of isdf_gga_b88 and the kernel's unique components
+    written out by isdf_gga_b88_fxc."""
+    be = mydf.backend
+    G = rho0.shape[1]
+    e, v = be.empty((1, G)), be.empty((4, G))
+    be.gga_b88(rho0[0], rho0[1:], e[0], v[0], v[1:])
+    f10 = be.empty((10, G))
+    be.gga_b88_fxc(rho0, None, None, fxc=f10)
+    f10 = be.to_host(f10)
+    sym = [[0, 1, 2, 3], [1, 4, 5, 6], [2, 5, 7, 8], [3, 6, 8, 9]]
+    return be.to_host(v), f10[np.array(sym)]
+
+
+def nr_rks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
+    """Closed-shell response matrix f_xc[rho0] rho1 (+ J[rho1]) of the matrices ``dms`` (multigrid.py:1259-1318): 'lda,', 'lda,vwn'
+    and 'b88,' (rho1 and grad rho1 from the ladder, the fused kernel on the dense mesh, the GGA integration pass)."""
+    kind = _response_kind(xc_code)
+    be = mydf.backend
+    nset = _nset_of(mydf, dms, kpts)
+    if kind == 'b88':
+        if fxc is not None:
+            return _response_gga(mydf, dms, kpts, _fxc_contract(mydf, fxc), with_j)
+        r0 = be.to_device(np.asarray(rho0, dtype=np.float64).reshape(4, -1)) if rho0 is not None \
+            else _ground_density_gga(mydf, dm0, kpts)[:, 0]
+        return _response_gga(mydf, dms, kpts, _b88_contract(mydf, r0), with_j)
     r0 = be.to_device(np.asarray(rho0, dtype=np.float64).reshape(1, -1)) if rho0 is not None else _ground_density(mydf, dm0, kpts)
-    nset = int(np.asarray(dms).size // (np.asarray(dm0).size))
-    return _response(mydf, dms, kpts, _kernel_rows(mydf, r0, fxc, nset), with_j)
+    return _response(mydf, dms, kpts, _kernel_rows(mydf, r0, fxc, nset, vwn=kind == 'vwn'), with_j)
 
 
 def nr_rks_fxc_st(mydf, xc_code, dm0, dms_alpha, singlet=True, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
     """Singlet / triplet response of the alpha-spin response matrices (multigrid.py:1321-1386): f_aa +- f_ab at rho_a = rho0/2.
-    For exchange alone f_ab = 0 and f_aa(rho0/2) = 2 f(rho0): singlet and triplet coincide."""
-    _check_lda(xc_code)
+    For exchange alone f_ab = 0 and f_aa(rho0/2) = 2 f(rho0): singlet and triplet coincide.  A caller's fxc is the open-shell
+    kernel (2, nx, 2, nx, G) of cache_xc_kernel1(spin=1).  'lda,vwn': the singlet only (f_aa + f_ab = 2 f(rho0))."""
+    kind = _response_kind(xc_code, open_shell=not singlet)
     be = mydf.backend
+    if kind == 'b88':
+        if fxc is not None:
+            f = np.asarray(fxc, dtype=np.float64)
+            f = f[0, :, 0] + f[0, :, 1] if singlet else f[0, :, 0] - f[0, :, 1]
+            return _response_gga(mydf, dms_alpha, kpts, _fxc_contract(mydf, f), False)
+        if rho0 is not None:
+            r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, 4, -1)[0])
+        else:
+            r0 = _ground_density_gga(mydf, dm0, kpts)[:, 0]
+        return _response_gga(mydf, dms_alpha, kpts, _b88_contract(mydf, r0), False, w_scale=2.0)
     if fxc is not None:
         f = np.asarray(fxc, dtype=np.float64)
         fxc = f[0, :, 0] + f[0, :, 1] if singlet else f[0, :, 0] - f[0, :, 1]
@@ -1022,28 +1191,57 @@ def nr_rks_fxc_st(mydf, xc_code, dm0, dms_alpha, singlet=True, rho0=None, vxc=No
         r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, -1)[:1])      # (rho_a, rho_b) in, total density out
     else:
         r0 = _ground_density(mydf, dm0, kpts)
-    nset = int(np.asarray(dms_alpha).size // (np.asarray(dm0).size))
-    return _response(mydf, dms_alpha, kpts, _kernel_rows(mydf, r0, fxc, nset), False, w_scale=1.0 if fxc is not None else 2.0)
+    nset = _nset_of(mydf, dms_alpha, kpts)
+    return _response(mydf, dms_alpha, kpts, _kernel_rows(mydf, r0, fxc, nset, vwn=kind == 'vwn'), False,
+                     w_scale=1.0 if fxc is not None else 2.0)
 
 
 def nr_uks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
     """Open-shell response (multigrid.py:1389-1452): dm0 = (alpha, beta), dms = (alpha responses..., beta responses...);
-    w_s = f_ss(rho0_s) rho1_s with f_ss(rho_s) = 2 f(2 rho_s) by spin scaling, the Coulomb term of with_j from rho1_a + rho1_b."""
-    _check_lda(xc_code)
-    if fxc is not None:
-        raise NotImplementedError('nr_uks_fxc with a caller-supplied kernel')
+    w_s = f_ss(rho0_s) rho1_s with f_ss(rho_s) = 2 f(2 rho_s) by spin scaling, the Coulomb term of with_j from rho1_a + rho1_b.
+    A caller's fxc is the kernel (2, nx, 2, nx, G) of cache_xc_kernel1(spin=1), applied block by block."""
+    kind = _response_kind(xc_code, open_shell=True)
     be = mydf.backend
+    if kind == 'b88':
+        if fxc is not None:
+            return _response_gga(mydf, dms, kpts, _fxc_contract_spins(mydf, fxc), with_j, total_j=True)
+        if rho0 is not None:
+            r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, 4, -1).transpose(1, 0, 2))
+        else:
+            r0 = _ground_density_gga(mydf, dm0, kpts, scale=2.0)
+        return _response_gga(mydf, dms, kpts, _b88_contract_spins(mydf, r0), with_j, total_j=True, w_scale=2.0)
+    if fxc is not None:
+        return _response(mydf, dms, kpts, None, with_j, total_j=True, contract=_fxc_contract_spins(mydf, fxc))
     r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, -1)) if rho0 is not None \
         else _ground_density(mydf, dm0, kpts, scale=2.0)
-    nset = int(np.asarray(dms).size // (np.asarray(dm0).size // 2))
+    nset = _nset_of(mydf, dms, kpts)
     return _response(mydf, dms, kpts, _kernel_rows(mydf, r0, None, nset), with_j, total_j=True, w_scale=2.0)
 
 
 def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
-    """(rho, vxc, fxc) of the ground state for the response functions (multigrid.py:1457-1500), array shapes of eval_xc_eff for
-    an LDA: spin 0 -> rho (G,), vxc (1, G), fxc (1, 1, G); spin 1 -> rho (2, G), vxc (2, 1, G), fxc (2, 1, 2, 1, G)."""
-    _check_lda(xc_code)
+    """(rho, vxc, fxc) of the ground state for the response functions (multigrid.py:1457-1500), array shapes of eval_xc_eff:
+    LDA ('lda,', 'lda,vwn' at spin 0): spin 0 -> rho (G,), vxc (1, G), fxc (1, 1, G); spin 1 -> rho (2, G), vxc (2, 1, G),
+    fxc (2, 1, 2, 1, G).  GGA ('b88,'): spin 0 -> rho (4, G), vxc (4, G), fxc (4, 4, G); spin 1 -> rho (2, 4, G), vxc (2, 4, G),
+    fxc (2, 4, 2, 4, G) (spin scaling: the cross-spin blocks are zero)."""
+    kind = _response_kind(xc_code, open_shell=spin == 1)
     be = mydf.backend
+    if kind == 'b88':
+        rho = _ground_density_gga(mydf, dm, kpts)                           # (4, n_dm, G)
+        if spin == 0:
+            if rho.shape[1] != 1:
+                raise ValueError('spin = 0 takes one density matrix')
+            r0 = rho[:, 0].contiguous()
+            v, f = _b88_kernel_host(mydf, r0)
+            return be.to_host(r0), v, f
+        r = be.to_host(rho).transpose(1, 0, 2)                               # (n_dm, 4, G)
+        if r.shape[0] == 1:
+            r = np.repeat(r, 2, axis=0) * .5
+        G = r.shape[2]
+        vx, fx = np.empty((2, 4, G)), np.zeros((2, 4, 2, 4, G))
+        for sp in range(2):
+            v, f = _b88_kernel_host(mydf, be.to_device(np.ascontiguousarray(2.0 * r[sp])))
+            vx[sp], fx[sp, :, sp] = v, 2.0 * f
+        return np.ascontiguousarray(r), vx, fx
     rho = _ground_density(mydf, dm, kpts)
     if spin == 0:
         if rho.shape[0] != 1:
@@ -1051,6 +1249,9 @@ def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
         e, v, f = be.empty(tuple(rho.shape)), be.empty(tuple(rho.shape)), be.empty(tuple(rho.shape))
         be.lda_exchange(rho[0], e[0], v[0])
         be.lda_exchange_fxc(rho[0], f[0])
+        if kind == 'vwn':
+            be.lda_vwn_add(rho[0], e[0], v[0])
+            be.lda_vwn_fxc_add(rho[0], f[0])
         return be.to_host(rho)[0], be.to_host(v), be.to_host(f)[None]
     r = be.to_host(rho)
     if r.shape[0] == 1:
@@ -1068,6 +1269,42 @@ def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
 
 def cache_xc_kernel(mydf, xc_code, mo_coeff, mo_occ, spin=0, kpts=None):
     raise NotImplementedError          # as the reference (multigrid.py:1454-1455)
+
+
+def _mf_kpts(mf):
+    if getattr(mf, 'kpts', None) is not None:
+        return np.asarray(mf.kpts, dtype=float).reshape(-1, 3)
+    return np.asarray(mf.kpt, dtype=float).reshape(1, 3)
+
+
+def _gen_rhf_response(mf, dm0, singlet=None, hermi=0):
+    """Closed-shell response function dm1 -> v1 for Newton / stability / TDDFT (multigrid.py:1503-1532): the kernel is cached once
+    (cache_xc_kernel1); singlet None gives f_xc rho1 + J[rho1] (nr_rks_fxc, the orbital Hessian of a closed shell), True / False the
+    singlet / triplet f_xc alone (nr_rks_fxc_st).  No exchange term: a hybrid caller adds ISDF.get_jk(dm1, with_j=False) itself.
+    ``mf`` needs .with_df, .xc and .kpts (or .kpt)."""
+    kpts = _mf_kpts(mf)
+    rho0, vxc, fxc = cache_xc_kernel1(mf.with_df, mf.xc, dm0, 0 if singlet is None else 1, kpts)
+
+    def vind(dm1):
+        if hermi == 2:
+            return np.zeros_like(dm1)
+        if singlet is None:
+            return nr_rks_fxc(mf.with_df, mf.xc, None, dm1, hermi, True, rho0, vxc, fxc, kpts)
+        return nr_rks_fxc_st(mf.with_df, mf.xc, None, dm1, singlet, rho0, vxc, fxc, kpts)
+    return vind
+
+
+def _gen_uhf_response(mf, dm0, with_j=True, hermi=0):
+    """Open-shell response function (multigrid.py:1534-1550): dm1 = (alpha responses..., beta responses...) -> nr_uks_fxc with the
+    cached spin-resolved kernel."""
+    kpts = _mf_kpts(mf)
+    rho0, vxc, fxc = cache_xc_kernel1(mf.with_df, mf.xc, dm0, 1, kpts)
+
+    def vind(dm1):
+        if hermi == 2:
+            return np.zeros_like(dm1)
+        return nr_uks_fxc(mf.with_df, mf.xc, None, dm1, hermi, with_j, rho0, vxc, fxc, kpts)
+    return vind
 
 
 def _nr_uks_gga(mydf, dm_in, with_j, return_j, kpts, kpts_band):
