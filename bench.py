@@ -1,15 +1,20 @@
 #!/usr/bin/env python
 """bench.py — ISDF build + 1x get_jk on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full [--no-accuracy] [--no-cpu-baseline]]
 
 One "step" = ISDF.build() (collocation, interpolation-point selection, fit, Coulomb W) followed by
 one get_jk() on a synthetic density matrix; the cell tables and the density matrix are already
 resident when the timed region starts.  N > 1 is launched by torch.distributed.run (one rank per
-GPU, RCCL).  Rank 0 prints ONE JSON line (see the contract in the task description) with two extra
-objects: "roofline" for the dominant hand-written kernel (measured live with HIP events on the work
-stream by the library's profiling hooks) and "cpu_baseline" (the numpy/scipy oracle timed on the
-host on a bounded sample of the same workload, extrapolated stage by stage).
+GPU, RCCL).  Rank 0 prints ONE JSON line (metric, value, unit, ms_per_step, ...) with an extra
+object "roofline" for the dominant hand-written kernel (measured live in the timed steps with HIP
+events on the work stream by the library's profiling hooks).
+
+A plain run does only that: set-up, warm-up, the timed steps, the optional dump and the line.
+--full adds what takes time of its own outside the steps: the accuracy entry (the exact exchange
+on the same GPU, before the warm-up) and "cpu_baseline" (the numpy/scipy oracle timed on the host
+on a bounded sample of the same workload, extrapolated stage by stage, after the timed steps);
+--no-accuracy and --no-cpu-baseline leave one of them out again.
 """
 import argparse
 import json
@@ -41,9 +46,11 @@ def parse_args():
     ap.add_argument('--refine-over', type=float, default=2.0)
     ap.add_argument('--cand-ao-cutoff', type=float, default=None,
                     help="Bohr: the candidate stage of the refined selection sees only the AOs of atoms this close to a block's atom (default: all)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the accuracy entry and cpu_baseline (off by default)')
     ap.add_argument('--no-accuracy', action='store_true',
-                    help="skip the exact-exchange comparison (config.dE_K_vs_exact; the reference's algorithm on the same GPU, "
-                         "about 40 s at configs[2], evaluated BEFORE the warm-up and timed steps)")
+                    help="with --full: skip the exact-exchange comparison (config.dE_K_vs_exact; the reference's algorithm on the "
+                         "same GPU, about 40 s at configs[2], evaluated BEFORE the warm-up and timed steps)")
     ap.add_argument('--pair-space', default='ao', choices=['ao', 'occ'],
                     help="'occ': fit the (AO x occupied orbital) pairs of the benchmark density (its mo_coeff/mo_occ tag, "
                          "fft_jk.py:206-210); the fit then runs inside get_jk, still inside the timed step")
@@ -57,7 +64,7 @@ def parse_args():
                     help="'random': BASELINE.json's benchmark density (random orthogonal orbitals; the headline); 'scf': physical "
                          "orbitals - an RHF converged with the ISDF object itself before anything is timed (hcore from the device, S and T "
                          "by plane-wave quadrature of the AO values); Gamma-point workloads, one GPU")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline (about 30 s on the host)')
     ap.add_argument('--stage-report', default=None, help='write the per-kernel table to this file')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='after the timed steps, write what the last timed step returned (vj, vk) as DIR/<name>.npy in float64 '
@@ -360,11 +367,11 @@ def main():
             last_note[0] = now
             print('[bench] %s step %d of %d done, %.0f s since start' % (what, i + 1, n, now - T_PROCESS_START), file=sys.stderr, flush=True)
 
-    # accuracy reference FIRST (outside every timed region): the reference's exact exchange (fft_jk.py:177-302, N*nocc FFT
-    # pairs) for the benchmark density on this GPU - measured in this run, never read from a file
+    # --full: accuracy reference FIRST (outside every timed region): the reference's exact exchange (fft_jk.py:177-302, N*nocc
+    # FFT pairs) for the benchmark density on this GPU - measured in this run, never read from a file
     vk_exact = None
     t_exact = 0.0
-    if kpts is None and not args.no_accuracy:
+    if kpts is None and args.full and not args.no_accuracy:
         print('[bench] exact exchange on the GPU for the accuracy entry (about 40 s)', file=sys.stderr, flush=True)
         ta = time.perf_counter()
         vk_exact = df.get_k_exact(mo_coeff=c_mo, mo_occ=occ_mo)      # N > 1: the AO rows of K are shared out over the ranks
@@ -525,7 +532,7 @@ def main():
                                        'c, the selection and the pair space'}
         if os.environ.get('ISDF_ONE_GPU'):
             out['data'] = 'synthetic; REHEARSAL: %d ranks on one GPU over gloo, not a benchmark' % world
-        if world == 1 and not args.no_cpu_baseline and kpts is None:
+        if world == 1 and args.full and not args.no_cpu_baseline and kpts is None:
             # threads the numpy/scipy oracle really uses = the BLAS pool of this interpreter (not os.cpu_count())
             try:
                 from threadpoolctl import threadpool_info

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence for bench.py's line, collected in ONE gpurun call from the same tree:
-#   1. the plain default bench (JSON line + per-kernel stage report)
+#   1. the default bench with --full (JSON line with the accuracy entry and cpu_baseline + per-kernel stage report)
 #   2. rocprofv3 --kernel-trace --stats of the same command (per-kernel durations)
 #   3. rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (they do not fit one pass on gfx950)
 # then tools/pmc_summarise.py folds 3 into one JSON.  Copy what is to be judged from gpurun_out/$TAG into profiles/.
@@ -12,7 +12,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 if [ -z "$PMC_ONLY" ]; then
-python3 bench.py $BENCH_ARGS --steps 2 --warmup 1 --stage-report $OUT/stage_report.txt > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py $BENCH_ARGS --full --steps 2 --warmup 1 --stage-report $OUT/stage_report.txt > $OUT/bench.json 2> $OUT/bench.err || exit 1
 echo "bench done: $(cut -c1-160 $OUT/bench.json)"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py $BENCH_ARGS --steps 1 --warmup 1 --no-cpu-baseline --no-accuracy > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || exit 1
 echo "stats done"
