@@ -279,6 +279,19 @@ int isdf_pair_prod_rows(isdf_handle h, const double* d_aoP, int P, int nao, cons
                         const double* d_ao, int64_t ld, const double* d_psi, int64_t ldpsi, int64_t ng,
                         double* d_B, int64_t ldb);
 int isdf_factor_solve_half(isdf_handle h, const double* d_fac, int P, int backward, double* d_X, int64_t n, int64_t ldx);
+/* The same at k-points (complex mode): pairs conj(u^k1_mu) psi~^k2_j of periodic parts, stacked as real
+ * rows like isdf_select_ip_cplx: d_aoP (P, nao) = [Re u | Im u] at the points (nao = 2 nh), d_psiP (P, npsi) = [Re psi~ | Im psi~]
+ * at the points (npsi = 2 npsi_h), d_ao (nao, ld) and d_psi (npsi, ldpsi) the same rows on the grid.  The Gram matrix is
+ * Re[S_u conj(S_psi)], with xP_rot = [Im xP | -Re xP]:
+ *   isdf_gram_prod_cplx       d_A (P, P)   = (aoP aoP^T) o (psiP psiP^T) + (aoP_rot aoP^T) o (psiP_rot psiP^T)
+ *   isdf_pair_prod_rows_cplx  d_B (P, ldb) = (aoP ao) o (psiP psi) + (aoP_rot ao) o (psiP_rot psi) on ng grid columns; grid
+ *                             slices are independent.  Scratch: column chunks of the two M = 2P products (<= 2 GiB).
+ * With psi = ao (every AO occupied with weight 1) both reduce to isdf_gram_sq / isdf_pair_gram_rows with nh. */
+int isdf_gram_prod_cplx(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_psiP, int npsi, int npsi_h,
+                        double* d_A);
+int isdf_pair_prod_rows_cplx(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_psiP, int npsi,
+                             int npsi_h, const double* d_ao, int64_t ld, const double* d_psi, int64_t ldpsi, int64_t ng,
+                             double* d_B, int64_t ldb);
 
 /* d_A <- d_A + shift_rel * max(diag d_A) * I. */
 int isdf_shift_diag(isdf_handle h, double* d_A, int P, double shift_rel);

@@ -280,6 +280,22 @@ class HipBackend:
         self.handle.call('isdf_pair_prod_rows', self._p(aoP), aoP.shape[0], aoP.shape[1], self._p(psiP), psiP.shape[1],
                          self._p(ao), ao.stride(0), self._p(psi), psi.stride(0), int(ng), self._p(B), B.stride(0))
 
+    def gram_prod_cplx(self, aoP, nh, psiP, npsi_h, A):
+        """k-point form: A (P, P) <- Re[S_u conj(S_psi)] at the points; aoP (P, 2 nh) and psiP (P, 2 npsi_h) stacked [Re | Im]."""
+        self._stream()
+        assert aoP.is_contiguous() and psiP.is_contiguous() and A.is_contiguous() and aoP.shape[0] == psiP.shape[0]
+        self.handle.call('isdf_gram_prod_cplx', self._p(aoP), aoP.shape[0], aoP.shape[1], int(nh), self._p(psiP), psiP.shape[1],
+                         int(npsi_h), self._p(A))
+
+    def pair_prod_rows_cplx(self, aoP, nh, psiP, npsi_h, ao, psi, ng, B):
+        """k-point form: B (P, ng) <- Re[S_u conj(S_psi)] between the points and ng grid columns; ao (2 nh, ld), psi (2 npsi_h, ld)."""
+        self._stream()
+        assert aoP.is_contiguous() and psiP.is_contiguous() and aoP.shape[0] == psiP.shape[0]
+        assert ao.stride(1) == 1 and psi.stride(1) == 1 and B.stride(1) == 1
+        self.handle.call('isdf_pair_prod_rows_cplx', self._p(aoP), aoP.shape[0], aoP.shape[1], int(nh), self._p(psiP),
+                         psiP.shape[1], int(npsi_h), self._p(ao), ao.stride(0), self._p(psi), psi.stride(0), int(ng), self._p(B),
+                         B.stride(0))
+
     def factor_solve_half(self, fac, backward, X):
         """X (P, n) <- L^-1 X (backward False) or L^-T X (backward True), A = L L^T (fac as stored by chol_inplace)."""
         self._stream()

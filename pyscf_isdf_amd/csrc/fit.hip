@@ -632,6 +632,125 @@ extern "C" int isdf_pair_prod_rows(isdf_handle h, const double* d_aoP, int P, in
   return ISDF_OK;
 }
 
+// ---- (AO x occupied orbital) pair space at k-points ------------------------------------------------------------
+// Periodic parts stacked as real rows [Re; Im] (isdf_select_ip_cplx): ao = [Re u; Im u] (2 nh rows), psi = [Re psi~; Im psi~]
+// (2 npsi_h rows).  With S_u = sum u(r) conj(u(r')) and S_psi likewise, the pair Gram matrix of conj(u) psi~ has the real part
+//   A = Re[S_u conj(S_psi)] = Re S_u Re S_psi + Im S_u Im S_psi,   Re S = xP x,  Im S = xP_rot x,  xP_rot = [Im xP | -Re xP],
+// so every product is a pair of real GEMMs with the rotated left factor, and the combine C = A0 o B0 + A1 o B1 is the pass
+// over the result that the hand-written kernel below makes.
+namespace {
+// C (rows, ldc) = A0 o B0 + A1 o B1 on `cols` columns (each operand with its own leading dimension).  Two columns per lane,
+// 16-byte loads and stores where the row addresses allow (wave-uniform: every operand row is 16-byte aligned or not), else
+// 8-byte ones.  C may be A0 or B0: each element is read before it is written by the same lane.
+__global__ __launch_bounds__(256) void prod_combine_kernel(const double* a0, int64_t lda0, const double* a1, int64_t lda1,
+                                                           const double* b0, int64_t ldb0, const double* b1, int64_t ldb1,
+                                                           double* c, int64_t ldc, int64_t cols) {
+  const int64_t col = 2 * ((int64_t)blockIdx.x * 256 + threadIdx.x);
+  const int64_t r = blockIdx.y;
+  if (col >= cols) return;
+  const double* pa0 = a0 + r * lda0 + col;
+  const double* pa1 = a1 + r * lda1 + col;
+  const double* pb0 = b0 + r * ldb0 + col;
+  const double* pb1 = b1 + r * ldb1 + col;
+  double* pc = c + r * ldc + col;
+  const uintptr_t mis = ((uintptr_t)pa0 | (uintptr_t)pa1 | (uintptr_t)pb0 | (uintptr_t)pb1 | (uintptr_t)pc) & 15;
+  if (mis == 0 && col + 1 < cols) {
+    const double2 x0 = *reinterpret_cast<const double2*>(pa0);
+    const double2 x1 = *reinterpret_cast<const double2*>(pa1);
+    const double2 y0 = *reinterpret_cast<const double2*>(pb0);
+    const double2 y1 = *reinterpret_cast<const double2*>(pb1);
+    double2 z;
+    z.x = fma(x1.x, y1.x, x0.x * y0.x);
+    z.y = fma(x1.y, y1.y, x0.y * y0.y);
+    *reinterpret_cast<double2*>(pc) = z;
+    return;
+  }
+  pc[0] = fma(pa1[0], pb1[0], pa0[0] * pb0[0]);
+  if (col + 1 < cols) pc[1] = fma(pa1[1], pb1[1], pa0[1] * pb0[1]);
+}
+// dst (2P, n): rows [0, P) = src (P, n), rows [P, 2P) = src_rot = [src[:, nh:] | -src[:, :nh]]  (n = 2 nh)
+__global__ void stack_rot_kernel(const double* __restrict__ src, int P, int nh, double* __restrict__ dst) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = blockIdx.y;
+  const int n = 2 * nh;
+  if (m >= n) return;
+  const double* s = src + (int64_t)p * n;
+  dst[(int64_t)p * n + m] = s[m];
+  dst[(int64_t)(P + p) * n + m] = (m < nh) ? s[nh + m] : -s[m - nh];
+}
+int prod_combine(isdf_handle h, const double* a0, int64_t lda0, const double* a1, int64_t lda1, const double* b0, int64_t ldb0,
+                 const double* b1, int64_t ldb1, double* c, int64_t ldc, int rows, int64_t cols) {
+  ProfScope ps(h, "prod_combine_kernel[byte]", 40.0 * (double)rows * (double)cols);
+  hipLaunchKernelGGL(prod_combine_kernel, dim3((unsigned)cdiv(cols, 512), (unsigned)rows), dim3(256), 0, h->stream, a0, lda0,
+                     a1, lda1, b0, ldb0, b1, ldb1, c, ldc, cols);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+}  // namespace
+
+extern "C" int isdf_gram_prod_cplx(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_psiP, int npsi,
+                                   int npsi_h, double* d_A) {
+  // A (P, P) = (aoP aoP^T) o (psiP psiP^T) + (aoP_rot aoP^T) o (psiP_rot psiP^T); the last three products in row chunks
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_aoP && d_psiP && d_A && P > 0 && P <= 65535 && nh > 0 && nao == 2 * nh && npsi_h > 0 && npsi == 2 * npsi_h);
+  int rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, d_aoP, nao, d_aoP, nao, 0.0, d_A, P);
+  if (rc) return rc;
+  double* ao2 = (double*)isdf_ws(h, "occk_ao2", sizeof(double) * (size_t)2 * P * nao);
+  double* psi2 = (double*)isdf_ws(h, "occk_psi2", sizeof(double) * (size_t)2 * P * npsi);
+  // three (rows x P) products per chunk in at most 2 GiB
+  const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(P, ((int64_t)1 << 28) / (3 * (int64_t)P)));
+  double* tmp = (double*)isdf_ws(h, "occk_tmp", sizeof(double) * (size_t)3 * CH * P);
+  if (!ao2 || !psi2 || !tmp) return ISDF_ERR_HIP;
+  hipLaunchKernelGGL(stack_rot_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, ao2);
+  hipLaunchKernelGGL(stack_rot_kernel, dim3((unsigned)cdiv(npsi, 256), (unsigned)P), dim3(256), 0, h->stream, d_psiP, P, npsi_h,
+                     psi2);
+  KERNEL_CHECK(h);
+  double* T1 = tmp;
+  double* U0 = tmp + CH * P;
+  double* U1 = tmp + 2 * CH * P;
+  for (int64_t r0 = 0; r0 < P; r0 += CH) {
+    const int nr = (int)std::min<int64_t>(CH, P - r0);
+    rc = gemm_rm(h, 'N', 'T', nr, P, nao, 1.0, ao2 + (P + r0) * nao, nao, d_aoP, nao, 0.0, T1, P);
+    if (!rc) rc = gemm_rm(h, 'N', 'T', nr, P, npsi, 1.0, psi2 + r0 * npsi, npsi, d_psiP, npsi, 0.0, U0, P);
+    if (!rc) rc = gemm_rm(h, 'N', 'T', nr, P, npsi, 1.0, psi2 + (P + r0) * npsi, npsi, d_psiP, npsi, 0.0, U1, P);
+    if (!rc) rc = prod_combine(h, d_A + r0 * P, P, T1, P, U0, P, U1, P, d_A + r0 * P, P, nr, P);
+    if (rc) return rc;
+  }
+  return ISDF_OK;
+}
+
+extern "C" int isdf_pair_prod_rows_cplx(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_psiP,
+                                        int npsi, int npsi_h, const double* d_ao, int64_t ld, const double* d_psi, int64_t ldpsi,
+                                        int64_t ng, double* d_B, int64_t ldb) {
+  // B (P, ng) = (aoP ao) o (psiP psi) + (aoP_rot ao) o (psiP_rot psi): per column chunk the two M = 2P products
+  // [aoP; aoP_rot] ao and [psiP; psiP_rot] psi, then one combine pass into B
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_aoP && d_psiP && d_ao && d_psi && d_B && P > 0 && P <= 65535 && nh > 0 && nao == 2 * nh && npsi_h > 0 &&
+               npsi == 2 * npsi_h && ng > 0);
+  ARG_CHECK(h, ld >= ng && ldpsi >= ng && ldb >= ng);
+  double* ao2 = (double*)isdf_ws(h, "occk_ao2", sizeof(double) * (size_t)2 * P * nao);
+  double* psi2 = (double*)isdf_ws(h, "occk_psi2", sizeof(double) * (size_t)2 * P * npsi);
+  // two (2P x CH) products in at most 2 GiB
+  int64_t CH = ((int64_t)1 << 26) / P;
+  CH = std::max<int64_t>(256, std::min<int64_t>(65536, CH)) / 256 * 256;
+  double* tmp = (double*)isdf_ws(h, "occk_tmp", sizeof(double) * (size_t)4 * P * CH);
+  if (!ao2 || !psi2 || !tmp) return ISDF_ERR_HIP;
+  hipLaunchKernelGGL(stack_rot_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, ao2);
+  hipLaunchKernelGGL(stack_rot_kernel, dim3((unsigned)cdiv(npsi, 256), (unsigned)P), dim3(256), 0, h->stream, d_psiP, P, npsi_h,
+                     psi2);
+  KERNEL_CHECK(h);
+  double* tA = tmp;
+  double* tB = tmp + 2 * P * CH;
+  for (int64_t c0 = 0; c0 < ng; c0 += CH) {
+    const int64_t nc = std::min(CH, ng - c0);
+    int rc = product_rows(h, 2 * P, nc, nao, ao2, d_ao + c0, ld, tA, CH, false);
+    if (!rc) rc = product_rows(h, 2 * P, nc, npsi, psi2, d_psi + c0, ldpsi, tB, CH, false);
+    if (!rc) rc = prod_combine(h, tA, CH, tA + P * CH, CH, tB, CH, tB + P * CH, CH, d_B + c0, ldb, P, nc);
+    if (rc) return rc;
+  }
+  return ISDF_OK;
+}
+
 extern "C" int isdf_factor_solve_half(isdf_handle h, const double* d_fac, int P, int backward, double* d_X, int64_t n,
                                       int64_t ldx) {
   // X (P, n) row-major <- L^-1 X (backward 0) or L^-T X (backward 1), A = L L^T (d_fac as in isdf_factor_solve): the two halves

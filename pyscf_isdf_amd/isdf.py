@@ -204,6 +204,7 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         self._Dinv = None
         self._Dinv_key = None
         self._kfit_state = None
+        self._ksel = None
         self._V = None
         self._Wq = None
         self._aoP_k = None
@@ -737,7 +738,9 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         m = len(cand)
         P_target = min(int(P_target), m)
         A = be.empty((m, m)) if gram is None else gram
-        if psiC is not None:
+        if psiC is not None and nh:
+            be.gram_prod_cplx(aoC, nh, psiC, psiC.shape[1] // 2, A)    # k-point (AO x occupied) pairs: psiC = [Re | Im] psi~
+        elif psiC is not None:
             be.gram_prod(aoC, psiC, A)
         else:
             be.gram_sq(aoC, A, nh)                  # nh > 0: k-point (complex) mode, aoC = [Re u | Im u] at the candidates

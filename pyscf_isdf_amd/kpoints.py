@@ -27,15 +27,11 @@ class KPointMixin:
         orbs = []
         for k in range(nk):
             if mo_coeff is not None:
-                occ = np.asarray(mo_occ[k], dtype=float)
-                orbs.append(np.asarray(mo_coeff[k])[:, occ > 0] * np.sqrt(occ[occ > 0]))
+                orbs.append(self._orbitals_from_tag(mo_coeff[k], mo_occ[k]))
             else:
-                d = np.asarray(dm).reshape(-1, nao, nao)[k]
-                ev, u = np.linalg.eigh(0.5 * (d + d.conj().T))
-                if ev.min() < -1e-10 * abs(ev).max():
+                orbs.append(self._orbitals_from_psd(np.asarray(dm).reshape(-1, nao, nao)[k]))
+                if orbs[-1] is None:
                     raise ValueError('get_k_exact needs occupied orbitals or positive semidefinite density matrices')
-                keep = ev > 1e-12 * ev.max()
-                orbs.append(u[:, keep] * np.sqrt(ev[keep]))
         i0, ni = (0, nao) if rows is None else (int(rows[0]), int(rows[1]))
         rcut = gto.estimate_rcut_per_shell(cell)
         Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
@@ -45,13 +41,8 @@ class KPointMixin:
         m2 = []
         for k in range(nk):                                     # occupied orbitals at k2 as periodic parts: m2 = C^T u
             be.eval_ao_k(*ao_args, kpts[k], True, coords_soa, u[0], u[1])
-            c = np.ascontiguousarray(orbs[k].T)                 # (nocc, nao)
-            cr, ci = be.to_device(np.ascontiguousarray(c.real)), be.to_device(np.ascontiguousarray(c.imag))
-            m = be.empty((2, c.shape[0], G))
-            be.gemm_nn(cr, u[0], m[0])
-            be.gemm_nn(ci, u[1], m[0], alpha=-1.0, beta=1.0)
-            be.gemm_nn(cr, u[1], m[1])
-            be.gemm_nn(ci, u[0], m[1], alpha=1.0, beta=1.0)
+            m = be.empty((2, orbs[k].shape[1], G))
+            self._orbitals_on_grid(u[0], u[1], orbs[k], m[0], m[1])
             m2.append(m)
         nocc_max = max(m.shape[1] for m in m2)
         if max_rows is None:
@@ -68,15 +59,27 @@ class KPointMixin:
             out[b] = be.to_host(vr) + 1j * be.to_host(vi)
         return out
 
+    def _kocc_eligible(self):
+        """pair_space='occ' at k-points: the (AO x occupied) pair space is fitted for select 'local' / 'refined' on one process
+        with the Cholesky fit route, without robust_k and without a kpts_symm.KPoints input; everything else keeps the Bloch
+        AO pairs."""
+        return (self.pair_space == 'occ' and self.select in ('local', 'refined') and self.comm.size == 1
+                and not getattr(self.comm, 'always', False) and not self.robust_k and not self.bj_auto_kpts
+                and self.kpts_symm is None and self.fit_route in ('auto', 'cholesky'))
+
     def _build_kpts(self):
         """Periodic parts u^k of all Bloch AOs -> real points/Theta (complex-mode S2/S3) -> one complex
         W^q per difference vector q = k2 - k1.  The q list is split over the ranks (each rank holds the
-        fit, builds its share of the W^q and later the K terms that use them)."""
+        fit, builds its share of the W^q and later the K terms that use them).  pair_space='occ' (_kocc_eligible): the build
+        stops after the density-independent per-atom candidates; get_jk makes the final pick, the fit and the W^q for the
+        occupied orbitals of its density (_ensure_fit_kpts)."""
         from . import pbc_tools
         cell, be, comm = self.cell, self.backend, self.comm
         self.timings = {}
-        if self.pair_space == 'occ':
-            warnings.warn("ISDF: pair_space='occ' is a Gamma-point option; the k-point build interpolates the Bloch AO pairs")
+        occ_pairs = self._kocc_eligible()
+        if self.pair_space == 'occ' and not occ_pairs:
+            warnings.warn("ISDF: pair_space='occ' at k-points needs select 'local' or 'refined', one process, the Cholesky fit "
+                          "route and no robust_k or kpts_symm; the k-point build interpolates the Bloch AO pairs")
         t0 = time.perf_counter()
         kpts_scf = np.asarray(self.kpts, dtype=float).reshape(-1, 3)
         # band k-points (kpts_band of get_jk) join the stack: the fit must also represent conj(u^{kb}) u^{k}
@@ -113,15 +116,16 @@ class KPointMixin:
         t0 = self._tick('S1_eval_ao', t0)
 
         # S2 selection (complex mode); the number of points scales with the number of distinct pair
-        # families: c_isdf * nao * nk by default (capped by the grid)
+        # families: c_isdf * nao * kfac by default (capped by the grid)
         kfac = self.k_ip_factor or min(nk, 2)
         P_target = int(min(self.c_isdf * nao * kfac, G))
+        sel = dict(P_target=P_target, kpts_scf=kpts_scf, band=band, kpts=kpts, nao=nao, nh=nh)
         if self.select == 'global':
             theta = self._buffer('theta', (P_target, G))
             piv = be.empty((1, P_target), dtype=torch.int64)
             rank = be.select_ip_cplx(X, nh, [0, G], [P_target], self.select_tol, self.tie_rtol, theta, piv)
-            ip_dev = piv[0, :int(rank[0])].contiguous()
-            self.ip = be.to_host(ip_dev).astype(np.int64)
+            sel['ip'] = be.to_host(piv[0, :int(rank[0])].contiguous()).astype(np.int64)
+            sel['rank'] = rank
         else:
             owner = be.partition_by_atom(coords, cell.atom_coords(), a)
             perm = np.argsort(owner, kind='stable').astype(np.int64)
@@ -139,14 +143,68 @@ class KPointMixin:
             rank = be.select_ip_cplx(Xs, nh, blk_off, nip, self.select_tol, self.tie_rtol, L, piv)
             del Xs, L
             piv_h = be.to_host(piv)
+            sel.update(owner=owner, nip_final=nip_final, rank=rank,
+                       per_atom=[perm[blk_off[b] + piv_h[b, :rank[b]]] for b in range(cell.natm)])
+        self._ksel = sel
+        self._built = True
+        self._k_built = kpts_scf.copy()
+        self._band_built = None if self.kpts_band is None else band.copy()
+        self._nk_stack = nk
+        if occ_pairs:
+            # the final pick ('refined'), the fit and the W^q need the occupied orbitals: made by get_jk (_ensure_fit_kpts)
+            self._tick('S2_select_candidates' if self.select == 'refined' else 'S2_select_ip', t0)
+            self._fit_pending = True
+            return self
+        self._kpts_pick_and_fit(None, t0)
+        return self
+
+    def _kpts_pick_and_fit(self, orbs, t0=None):
+        """S2 second stage + S3 + S4 + S5 of the k-point build from the selection in self._ksel.  orbs None: the Bloch AO pairs;
+        else, per SCF k-point, the (N, nocc_k) complex coefficients C sqrt(occ) of the density's occupied orbitals: the
+        (AO x occupied) pair space conj(u^{k1}_mu) psi~^{k2}_j, psi~^k = sum_nu u^k_nu C^k_nu,j."""
+        from . import pbc_tools
+        cell, be, comm = self.cell, self.backend, self.comm
+        if t0 is None:
+            t0 = time.perf_counter()
+        sel = self._ksel
+        X = self.ao
+        P_target, kpts_scf, band, kpts, nao, nh = (sel[k] for k in ('P_target', 'kpts_scf', 'band', 'kpts', 'nao', 'nh'))
+        nk = len(kpts)
+        coords = self.grids.coords
+        G = X.shape[1]
+        self._W_omega = {}
+        Psi = psiP = None
+        if orbs is not None:
+            # psi~ on the grid, stacked like the periodic parts: rows [Re psi~ (all k, all j); Im psi~]
+            nocc_k = [c.shape[1] for c in orbs]
+            npsi_h = int(sum(nocc_k))
+            Psi = self._buffer('psik', (2 * npsi_h, G))
+            o = 0
+            for k, c in enumerate(orbs):
+                if c.shape[1]:
+                    self._orbitals_on_grid(X[k * nao:(k + 1) * nao], X[nh + k * nao:nh + (k + 1) * nao], c,
+                                           Psi[o:o + c.shape[1]], Psi[npsi_h + o:npsi_h + o + c.shape[1]])
+                o += c.shape[1]
+            t0 = self._tick('S2_occupied_on_grid', t0)
+        if self.select == 'global':
+            self.ip = sel['ip']
+            ip_dev = be.to_device(self.ip)
+        else:
+            rank = sel['rank']
             clusters = self._bj_clusters()
-            per_atom = [perm[blk_off[b] + piv_h[b, :rank[b]]] for b in range(cell.natm)]
+            per_atom = sel['per_atom']
             if self.select == 'refined':
+                owner = sel['owner']
                 cand = np.concatenate(per_atom).astype(np.int64)
                 aoC = be.empty((len(cand), 2 * nh))
-                be.gather_aoP(X, be.to_device(cand), aoC)
-                chosen = self._refine_pick(aoC, cand, int(nip_final.sum()), nh=nh)
-                del aoC
+                d_cand = be.to_device(cand)
+                be.gather_aoP(X, d_cand, aoC)
+                psiC = None
+                if Psi is not None:
+                    psiC = be.empty((len(cand), Psi.shape[0]))
+                    be.gather_aoP(Psi, d_cand, psiC)
+                chosen = self._refine_pick(aoC, cand, int(sel['nip_final'].sum()), nh=nh, psiC=psiC)
+                del aoC, psiC
                 own = owner[chosen]
                 per_atom = [chosen[own == b] for b in range(cell.natm)]
                 rank = np.array([len(x) for x in per_atom], dtype=np.int32)
@@ -162,7 +220,7 @@ class KPointMixin:
         # the primaries dealt round-robin over the ranks
         self._qs, self._qindex = pbc_tools.unique_q(kpts_scf, band)      # index[k1 in band][k2 in kpts]
         nq = len(self._qs)
-        w = cell.vol / G
+        mesh = np.asarray(self.mesh, dtype=np.int32)
         batch = self.fft_batch or max(1, min(P, int((4 << 30) // (8 * G)) // 256 * 256 or int((4 << 30) // (8 * G)) // 128 * 128 or 64))   # 256-row multiples: the 256x128 GEMM tile
         partner = -np.ones(nq, dtype=int)
         for iq in range(nq):
@@ -191,13 +249,27 @@ class KPointMixin:
         # Jacobi, verified on W^{q=0}, Cholesky when the check fails (the fit is replicated, so every rank takes the
         # agreed decision after its share of the q list)
         routes = self._fit_routes() if self.select != 'global' else ['cholesky']
-        if (self.fit_route == 'auto' and not self.bj_auto_kpts) or self._want_theta:
+        if (self.fit_route == 'auto' and not self.bj_auto_kpts) or self._want_theta or Psi is not None:
             routes = ['cholesky']
         for route in routes:
             if route == 'blockjacobi':
                 ip_off = self._bj_blocks(rank, clusters)
                 Afac, Dblk = self._bj_prepare(X, nh, ip_dev, ip_off, aoP_X)
                 self._bj_rows(aoP_X, nh, X, G, Dblk, ip_off, Y)
+            elif Psi is not None:
+                # (AO x occupied) pairs: A_PP = Re[S_u conj(S_psi)] at the points, the rows B likewise, Y = L^-1 B
+                chol = self._buffer('factor', (P, P))
+                be.gather_aoP(X, ip_dev, aoP_X)
+                psiP = be.empty((P, Psi.shape[0]))
+                be.gather_aoP(Psi, ip_dev, psiP)
+                be.gram_prod_cplx(aoP_X, nh, psiP, Psi.shape[0] // 2, chol)
+                be.shift_diag(chol, self.reg_rel)
+                self.reg_used = self.reg_rel + be.chol_inplace(chol, 0.0, scratch=self._buffer('Wre', (P, P)))
+                be.pair_prod_rows_cplx(aoP_X, nh, psiP, Psi.shape[0] // 2, X, Psi, G, Y)
+                be.factor_solve_half(chol, False, Y)
+                if self._want_theta:
+                    be.factor_solve_half(chol, True, Y)
+                del psiP
             else:
                 chol = self._buffer('factor', (P, P))
                 self.reg_used = be.fit_prepare_cplx(X, nh, ip_dev, self.reg_rel, aoP_X, chol)
@@ -224,11 +296,91 @@ class KPointMixin:
             self._aoP_k.append(be.to_device(np.ascontiguousarray(u * np.exp(1j * r_ip.dot(kpts[k]))[:, None])))
         self._q_partner = partner
         t0 = self._tick('S4S5_coulomb_W', t0)
-        self._built = True
-        self._k_built = kpts_scf.copy()
-        self._band_built = None if self.kpts_band is None else band.copy()
-        self._nk_stack = nk
         return self
+
+    # ---- pair_space='occ' at k-points: the fit follows the density ------------------------------------------------
+    @staticmethod
+    def _orbitals_from_tag(mo_coeff, mo_occ):
+        """(N, nocc) coefficients C sqrt(occ) of the occupied orbitals of one k-point (pyscf/pbc/df/fft_jk.py:206-210)."""
+        occ = np.asarray(mo_occ, dtype=float)
+        return np.asarray(mo_coeff)[:, occ > 0] * np.sqrt(occ[occ > 0])
+
+    @staticmethod
+    def _orbitals_from_psd(d):
+        """(N, r) orbitals u sqrt(ev) of a Hermitian positive semidefinite matrix from its eigenvectors; None when it is not
+        positive semidefinite."""
+        ev, u = np.linalg.eigh(0.5 * (d + d.conj().T))
+        if ev.min() < -1e-10 * abs(ev).max():
+            return None
+        keep = ev > 1e-12 * ev.max()
+        return u[:, keep] * np.sqrt(ev[keep])
+
+    def _orbitals_on_grid(self, ur, ui, orb, out_re, out_im):
+        """psi~ = C^T u^k on the grid (periodic parts of the orbitals orb (N, nocc) complex): the real and imaginary planes
+        (nocc, G) from those of u^k, four real products."""
+        be = self.backend
+        c = np.ascontiguousarray(orb.T)                 # (nocc, nao)
+        cr, ci = be.to_device(np.ascontiguousarray(c.real)), be.to_device(np.ascontiguousarray(c.imag))
+        be.gemm_nn(cr, ur, out_re)
+        be.gemm_nn(ci, ui, out_re, alpha=-1.0, beta=1.0)
+        be.gemm_nn(cr, ui, out_im)
+        be.gemm_nn(ci, ur, out_im, alpha=1.0, beta=1.0)
+
+    def _kpoint_occupied(self, dm, nk):
+        """Per SCF k-point, the (N, nocc_k) complex coefficients C sqrt(occ) of the density get_jk was called with: from its
+        per-k-point mo_coeff / mo_occ tag (shaped (nk, N, nmo) / (nk, nmo), or with a leading nset axis), else from the
+        eigenvectors of Hermitian positive semidefinite density matrices (nk, N, N) or (nset, nk, N, N).  Several sets (the
+        spins of a KUHF density): their orbitals side by side, as at the Gamma point.  None when the density has no such form
+        (a response or difference density, or rank > N/2 at some k-point): the Bloch AO pairs are fitted then."""
+        nao = self.cell.nao_nr()
+        mo_coeff, mo_occ = getattr(dm, 'mo_coeff', None), getattr(dm, 'mo_occ', None)
+        cols = [[] for _ in range(nk)]
+        if mo_coeff is not None and mo_occ is not None:
+            sets = [(mo_coeff, mo_occ)] if np.ndim(mo_occ[0]) == 1 else list(zip(mo_coeff, mo_occ))
+            for cs, os_ in sets:
+                if len(cs) != nk or len(os_) != nk:
+                    return None
+                for k in range(nk):
+                    cols[k].append(self._orbitals_from_tag(cs[k], os_[k]))
+        else:
+            dms = np.asarray(dm).reshape(-1, nk, nao, nao)
+            for s in range(dms.shape[0]):
+                for k in range(nk):
+                    d = dms[s, k]
+                    if abs(d - d.conj().T).max() > 1e-10 * max(abs(d).max(), 1e-300):
+                        return None
+                    c = self._orbitals_from_psd(d)
+                    if c is None:
+                        return None
+                    cols[k].append(c)
+        out = [np.ascontiguousarray(np.hstack(c), dtype=np.complex128) for c in cols]
+        if sum(c.shape[1] for c in out) == 0 or any(c.shape[1] > nao // 2 for c in out):
+            return None
+        return out
+
+    def _ensure_fit_kpts(self, dm=None):
+        """pair_space='occ' at k-points (_kocc_eligible): make sure the fit suits what is about to be contracted with the W^q,
+        as isdf.ISDF._ensure_fit does at the Gamma point.  dm with an occupied-orbital form: the (AO x occupied) pair space of
+        THAT density - refit when its occupied space differs from the fitted one (occ_refit='always') or keep the first such
+        fit ('once').  dm None (get_ao_eri / ao2mo) or a density without such a form: the Bloch AO pairs."""
+        if getattr(self, '_ksel', None) is None or not self._kocc_eligible():
+            return
+        nk = len(self._ksel['kpts_scf'])
+        orbs = None if dm is None else self._kpoint_occupied(dm, nk)
+        want = None if orbs is None else np.array([c.dot(c.conj().T) for c in orbs])
+        if not self._fit_pending:
+            have = self._fit_dm
+            if want is None:
+                if have is None:
+                    return                                            # the AO-pair fit is in place
+            elif have is None:
+                if self.occ_refit == 'once':
+                    return                                            # an AO-pair fit came first and is kept
+            elif self.occ_refit == 'once' or abs(want - have).max() <= 1e-12 * abs(want).max():
+                return
+        self._fit_dm = want
+        self._kpts_pick_and_fit(orbs)
+        self._fit_pending = False
 
     def _keep_Wq(self, Wc):
         """A finished W^q stays on the device while there is room for the rest of the build and for get_jk's work areas (about
@@ -386,6 +538,8 @@ class KPointMixin:
             self.kpts = kpts
             self.kpts_band = band
             self.build()
+        if with_k:
+            self._ensure_fit_kpts(dm)                            # pair_space='occ': the fit for this density's occupied orbitals
         nk = len(kpts)
         nks = self._nk_stack                                     # k-points in the stacked periodic parts
         bidx = list(range(nk)) if band is None else list(self._band_index)
@@ -412,10 +566,10 @@ class KPointMixin:
         if omega:
             # range separation: same fit, the W^q rebuilt with the attenuated kernel once per omega (until the next build)
             key = round(float(omega), 10)
-            if key not in self._W_omega:
+            if key not in self._W_omega and self._kfit_state is not None:       # (no fit yet: pair_space='occ', J alone)
                 self._W_omega[key], _, t0 = self._build_Wq(omega, t0)
                 t0 = self._tick('S4S5_coulomb_W_omega', t0)
-            Wq_set = self._W_omega[key]
+            Wq_set = self._W_omega.get(key)
             be.set_coulomb_omega(omega)                          # the J kernel table lives on the device
         elif ex == 'vcut_sph' and with_k:
             # exchange with the spherically truncated kernel (pbc.py:312-317, Rc from the nk-fold cell): its own W^q set
@@ -612,6 +766,7 @@ class KPointMixin:
             self.kpts = uniq
             self.kpts_band = None
             self.build()                     # through build(): drops the state (range-separated W^q included) of the old k-point set
+        self._ensure_fit_kpts()              # pair_space='occ': integrals come from the Bloch AO pairs
         iq = self._qindex[idx[0], idx[1]]
         Wq = self._Wq[iq] if iq in self._Wq else torch.conj_physical(self._Wq[self._q_partner[iq]])
         Wq = be.to_host(Wq)
