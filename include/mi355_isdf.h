@@ -70,7 +70,13 @@ int isdf_release_workspace(isdf_handle h);
  * "coul_sphere": p > 0 zeroes the Gamma-point kernel table beyond p percent of the radius of the sphere inscribed in the reciprocal
  * FFT box (0, the default: the whole box) - the experiment behind the spectral form of W (profiles/r03_sphere_check.log).
  * "gram_pivot_tpb": columns per workgroup of isdf_select_ip_gram's pivot step, 256 (default), 128 or 64; same pivots and
- * factor for every value, narrower is slower (12.2 / 13.0 / 15.5 us per pivot, profiles/r03_gram_pivot_step_widths.log). */
+ * factor for every value, narrower is slower (12.2 / 13.0 / 15.5 us per pivot, profiles/r03_gram_pivot_step_widths.log).
+ * "gram_compact": 1 (default) isdf_select_ip_gram moves the candidates not yet pivoted to the front of its stored order at a panel
+ * boundary once they fall below "gram_compact_permille" / 1000 of it (1..1000, default 875; 1000 compacts after every panel that
+ * took a pivot), so that trailing updates and pivot steps skip pivoted columns; 0 keeps the whole matrix.  Same pivots either way.
+ * The compaction stages 512 rows at a time in memory of its own (512 x m doubles at most, released before the call returns); if
+ * that allocation fails, a line on stderr says so and the pick goes on over the whole matrix.  With profiling enabled, every
+ * compaction adds to the "gram_compact[byte]" entry. */
 int isdf_set_option(isdf_handle h, const char* key, int value);
 /* Range separation of the Gamma-point Coulomb kernel used by isdf_coulomb_W / _rows / _potential / isdf_get_j, as
  * pyscf/pbc/tools/pbc.py:408-418: omega > 0 long range (erf(omega r)/r), omega < 0 short range, 0 (default) plain 1/r.
@@ -168,7 +174,8 @@ int isdf_select_ip(isdf_handle h, const double* d_ao, int nao, int64_t ld,
                    double* d_L, int64_t ldL, int64_t* d_piv, int32_t* rank);
 
 /* S2, refined stage: pivoted Cholesky of an EXPLICIT symmetric positive semidefinite matrix d_A (m x m, row-major,
- * leading dimension ldA, DESTROYED: it ends as the residual matrix) — the arithmetic of the reference's
+ * leading dimension ldA, DESTROYED: it ends as scratch - the residual of the last stored order, which "gram_compact" may have
+ * reduced to the columns not yet pivoted, in a permuted layout; no caller may read it) — the arithmetic of the reference's
  * pivoted_cholesky_python (pyscf/lib/scipy_helper.py:71-110) applied to the matrix itself, organised in panels of
  * ``panel`` pivots (<= 256; <= 0: 256) with a trailing update A <- A - Lp^T Lp after each panel (LAPACK dpstrf's scheme).
  * Used on the pair-density Gram matrix restricted to a candidate set of grid points (isdf_gram_sq of the candidates'

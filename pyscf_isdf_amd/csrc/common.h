@@ -62,6 +62,10 @@ struct isdf_ctx {
   int conv_pipe = 1;         // plane passes of the convolution: 1 persistent workgroups with the next plane prefetched, 0 one workgroup per plane
   int conv_sub_rows = 0;     // rows per cache-resident sub-batch of the plane convolution (0: whole batch)
   int gram_pivot_tpb = 256;  // columns per workgroup of the Gram selection's pivot step (64, 128 or 256: measured 15.5 / 13.0 / 12.2 us per pivot)
+  // Gram selection: 1 = move the columns not yet pivoted to the front of the stored order once they fall below
+  // gram_compact_permille / 1000 of it, so that the trailing updates and the pivot steps skip the pivoted ones (default); 0 = never
+  int gram_compact = 1;
+  int gram_compact_permille = 875;
   int block_apply_waves = 16;// grid of the register block apply: workgroups ~ this many times the CU count
   int block_apply_reg = 1;   // block apply with the block inverse in registers, persistent over column tiles (trsm.hip)
   // range-separation parameter of the Gamma-point Coulomb kernel table (0 = plain 1/r); isdf_set_coulomb_omega

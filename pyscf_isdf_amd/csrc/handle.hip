@@ -104,6 +104,12 @@ int isdf_set_option(isdf_handle h, const char* key, int value) {
     h->gram_pivot_tpb = value;
     return ISDF_OK;
   }
+  if (std::string(key) == "gram_compact") { h->gram_compact = value ? 1 : 0; return ISDF_OK; }
+  if (std::string(key) == "gram_compact_permille") {
+    if (value < 1 || value > 1000) return isdf_fail(h, ISDF_ERR_ARG, "isdf_set_option: gram_compact_permille %d not in [1, 1000]", value);
+    h->gram_compact_permille = value;
+    return ISDF_OK;
+  }
   if (std::string(key) == "block_apply_waves") { h->block_apply_waves = value < 1 ? 1 : value; return ISDF_OK; }
   if (std::string(key) == "block_apply_reg") { h->block_apply_reg = value ? 1 : 0; return ISDF_OK; }
   return isdf_fail(h, ISDF_ERR_ARG, "isdf_set_option: unknown key '%s'", key);

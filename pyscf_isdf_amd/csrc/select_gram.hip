@@ -213,6 +213,68 @@ __global__ __launch_bounds__(TPB) void gram_pivot_step_kernel(
   }
 }
 
+// ---- compaction of the stored order onto the columns not yet pivoted ----
+// map[i'] (ascending, i' < mc) = the stored index of the i'-th remaining column.  The residual diagonal moves into the other
+// buffer and its per-workgroup maxima are rebuilt for the new width, exactly as the pivot step would have written them.
+template <int TPB>
+__global__ __launch_bounds__(TPB) void gram_compact_diag_kernel(const double* __restrict__ d_src, const int32_t* __restrict__ map,
+                                                               int mc, double* __restrict__ d_dst, double* __restrict__ wgmax) {
+  __shared__ double red[TPB / 64];
+  const int i = blockIdx.x * TPB + threadIdx.x;
+  double v = 0.0;
+  if (i < mc) {
+    v = d_src[map[i]];
+    d_dst[i] = v;
+  }
+  double mx = wmax(i < mc ? fmax(v, 0.0) : 0.0);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < TPB / 64; ++w) mx = fmax(mx, red[w]);
+    wgmax[blockIdx.x] = mx;
+  }
+}
+
+// pivots [j0, j1) were written as indices of a compacted order: to original candidate indices
+__global__ __launch_bounds__(256) void gram_piv_to_original_kernel(int64_t* __restrict__ piv, int j0, int j1,
+                                                                   const int32_t* __restrict__ cmap) {
+  const int j = j0 + blockIdx.x * 256 + threadIdx.x;
+  if (j < j1) piv[j] = cmap[piv[j]];
+}
+
+// Rows [r0, r0 + nrows) of the compacted block-lower part (row r' keeps the columns up to the end of its own new strip) gathered
+// into S (nrows x lds) through the symmetric read rule of the OLD order.  Every read lies in a stored row >= r0 (map[r'] >= r',
+// and a transposed read map[i'] > map[r']), so once the chunks are written back in ascending order no source is overwritten
+// before it is read.
+__global__ __launch_bounds__(256) void gram_compact_gather_kernel(const double* __restrict__ A, int64_t ldA,
+                                                                  const int32_t* __restrict__ map, int mc, int r0,
+                                                                  double* __restrict__ S, int64_t lds) {
+  const int r = r0 + blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int ncol = min(mc, (r / SW + 1) * SW);
+  if (i >= ncol) return;
+  const int mr = map[r], mi = map[i];
+  S[(int64_t)blockIdx.y * lds + i] = (mr >= (mi / SW) * SW) ? A[(int64_t)mr * ldA + mi] : A[(int64_t)mi * ldA + mr];
+}
+
+__global__ __launch_bounds__(256) void gram_compact_store_kernel(const double* __restrict__ S, int64_t lds, int mc, int r0,
+                                                                 double* __restrict__ A, int64_t ldA) {
+  const int r = r0 + blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int ncol = min(mc, (r / SW + 1) * SW);
+  if (i >= ncol) return;
+  A[(int64_t)r * ldA + i] = S[(int64_t)blockIdx.y * lds + i];
+}
+
+}  // namespace
+
+namespace {
+// the staging rows of a compaction: device memory of this call only (released on every return)
+struct DeviceBuffer {
+  void* p = nullptr;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+};
+constexpr int COMPACT_ROWS = 512;   // rows per staging chunk (a divisor of SW): 512 * m' doubles, 215 MB at m' = 52 416
 }  // namespace
 
 extern "C" int isdf_select_ip_gram(isdf_handle h, double* d_A, int m, int64_t ldA, int nip, double tol,
@@ -224,12 +286,12 @@ extern "C" int isdf_select_ip_gram(isdf_handle h, double* d_A, int m, int64_t ld
   ARG_CHECK(h, panel <= PANEL_MAX);
   if (nip > m) nip = m;
   const int TPB = h->gram_pivot_tpb;
-  const int nwg = (int)cdiv(m, TPB);
+  int nwg = (int)cdiv(m, TPB);
   const int64_t ldL = ((int64_t)m + 31) / 32 * 32;
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t b_d = al(sizeof(double) * m), b_w = al(sizeof(double) * nwg), b_st = al(sizeof(GramState));
-  const size_t b_L = al(sizeof(double) * (size_t)panel * ldL);
-  char* ws = (char*)isdf_ws(h, "select_gram", 2 * b_d + 2 * b_w + b_st + b_L);
+  const size_t b_L = al(sizeof(double) * (size_t)panel * ldL), b_map = al(sizeof(int32_t) * m);
+  char* ws = (char*)isdf_ws(h, "select_gram", 2 * b_d + 2 * b_w + b_st + b_L + 3 * b_map);
   if (!ws) return ISDF_ERR_HIP;
   double* d_d[2];
   double* d_w[2];
@@ -238,21 +300,45 @@ extern "C" int isdf_select_ip_gram(isdf_handle h, double* d_A, int m, int64_t ld
   d_w[0] = (double*)ws; ws += b_w;
   d_w[1] = (double*)ws; ws += b_w;
   GramState* d_st = (GramState*)ws; ws += b_st;
-  double* d_Lp = (double*)ws;
+  double* d_Lp = (double*)ws; ws += b_L;
+  int32_t* d_map = (int32_t*)ws; ws += b_map;    // compacted -> previous stored order (one compaction)
+  int32_t* d_cmap[2];                             // compacted -> original candidate index (what piv reports), alternating
+  d_cmap[0] = (int32_t*)ws; ws += b_map;
+  d_cmap[1] = (int32_t*)ws;
   HIP_TRY(h, hipMemsetAsync(d_st, 0, sizeof(GramState), h->stream));
   HIP_TRY(h, hipMemsetAsync(d_piv, 0xff, sizeof(int64_t) * (size_t)nip, h->stream));
   if (TPB == 64) hipLaunchKernelGGL(gram_diag_kernel<64>, dim3(nwg), dim3(64), 0, h->stream, d_A, ldA, m, d_d[0], d_w[0]);
   else if (TPB == 128) hipLaunchKernelGGL(gram_diag_kernel<128>, dim3(nwg), dim3(128), 0, h->stream, d_A, ldA, m, d_d[0], d_w[0]);
   else hipLaunchKernelGGL(gram_diag_kernel<256>, dim3(nwg), dim3(256), 0, h->stream, d_A, ldA, m, d_d[0], d_w[0]);
   KERNEL_CHECK(h);
+  // Stored order: ms columns (at first all m candidates); cmap_h[i] = the original index of stored column i once compacted.
+  // Pivoted columns keep a residual diagonal of -1 and are never read again, yet the trailing update would go on carrying them:
+  // when the columns not yet pivoted fall below gram_compact_permille / 1000 of ms, they are moved to the front (stable, so the
+  // lowest-index tie rule picks the same original column) and ms shrinks to their number.  The pivot step writes stored
+  // indices; the pivots of each stretch between compactions are translated to original ones once the stretch ends.
+  int ms = m;
+  int rank_at_compact = 0;
+  int cc = -1;   // d_cmap[cc] holds the current stored order's map (-1: the original order)
+  auto piv_to_original = [&](int j1) -> int {
+    if (cc < 0 || j1 <= rank_at_compact) return ISDF_OK;
+    hipLaunchKernelGGL(gram_piv_to_original_kernel, dim3((unsigned)cdiv(j1 - rank_at_compact, 256)), dim3(256), 0, h->stream,
+                       d_piv, rank_at_compact, j1, (const int32_t*)d_cmap[cc]);
+    KERNEL_CHECK(h);
+    return ISDF_OK;
+  };
+  std::vector<int32_t> cmap_h, map_h;
+  std::vector<double> d_h;
+  bool compact = h->gram_compact != 0;
+  DeviceBuffer stage;
+  int64_t stage_ld = 0;
   int cur = 0;
   for (int k0 = 0; k0 < nip; k0 += panel) {
     const int nb = nip - k0 < panel ? nip - k0 : panel;
     {
-      ProfScope ps(h, "gram_pivot_step_kernel[byte]", 8.0 * (double)m * (0.5 * nb * (nb - 1) + 4.0 * nb), nb);
+      ProfScope ps(h, "gram_pivot_step_kernel[byte]", 8.0 * (double)ms * (0.5 * nb * (nb - 1) + 4.0 * nb), nb);
       for (int jl = 0; jl < nb; ++jl) {
 #define ISDF_GRAM_STEP(T)                                                                                              \
-  hipLaunchKernelGGL(gram_pivot_step_kernel<T>, dim3(nwg), dim3(T), 0, h->stream, d_A, ldA, m, d_Lp, ldL, d_d[cur],     \
+  hipLaunchKernelGGL(gram_pivot_step_kernel<T>, dim3(nwg), dim3(T), 0, h->stream, d_A, ldA, ms, d_Lp, ldL, d_d[cur],    \
                      d_d[cur ^ 1], d_w[cur], d_w[cur ^ 1], nwg, k0 + jl, jl, nip, tol, tie_rtol, d_st, d_piv)
         if (TPB == 64) ISDF_GRAM_STEP(64);
         else if (TPB == 128) ISDF_GRAM_STEP(128);
@@ -264,20 +350,81 @@ extern "C" int isdf_select_ip_gram(isdf_handle h, double* d_A, int m, int64_t ld
     }
     // one host synchronisation per panel: at most `panel` launches are ever outstanding.  Unbounded, the ~20 000
     // back-to-back launches of a configs[2] selection overran rocprofv3's counter-collection path (SIGSEGV in the tool at the
-    // first page past one of its buffers, profiles/r02_rocprofv3_pmc_abort_in_select_ip_gram.log); costs < 2 ms per build
+    // first page past one of its buffers, profiles/r02_rocprofv3_pmc_abort_in_select_ip_gram.log); costs < 2 ms per build.
+    // The rank rides along with it, so that the compaction is decided while the queue is empty.
+    GramState hst;
+    HIP_TRY(h, hipMemcpyAsync(&hst, d_st, sizeof(GramState), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (k0 + nb < nip) {
-      // trailing update A <- A - Lp^T Lp on the block-lower part: strip [c0, c1) from its first row down
-      for (int c0 = 0; c0 < m; c0 += SW) {
-        const int c1 = c0 + SW < m ? c0 + SW : m;
-        int rc = gemm_rm(h, 'T', 'N', m - c0, c1 - c0, nb, -1.0, d_Lp + c0, ldL, d_Lp + c0, ldL, 1.0,
-                         d_A + (int64_t)c0 * ldA + c0, ldA);
-        if (rc != ISDF_OK) return rc;
+    if (k0 + nb >= nip) break;
+    int mc = ms;
+    if (compact && !hst.done && ((int64_t)ms - (hst.rank - rank_at_compact)) * 1000 < (int64_t)ms * h->gram_compact_permille) {
+      // the remaining columns, ascending, from the sign of the residual diagonal: -1 marks a pivot (a negative initial diagonal,
+      // which the pivot step never updates nor picks, goes as well)
+      d_h.resize(ms);
+      HIP_TRY(h, hipMemcpyAsync(d_h.data(), d_d[cur], sizeof(double) * ms, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      map_h.clear();
+      for (int i = 0; i < ms; ++i)
+        if (!(d_h[i] < 0.0)) map_h.push_back(i);
+      mc = (int)map_h.size();
+      if (mc > 0 && mc < ms && !stage.p) {   // the first compaction is the widest
+        stage_ld = ((int64_t)mc + 31) / 32 * 32;
+        if (hipMalloc(&stage.p, sizeof(double) * (size_t)COMPACT_ROWS * stage_ld) != hipSuccess) {
+          (void)hipGetLastError();
+          stage.p = nullptr;
+          fprintf(stderr, "mi355_isdf: isdf_select_ip_gram: no device memory for the compaction's staging rows (%zu bytes); "
+                          "the pick goes on over the whole matrix\n", sizeof(double) * (size_t)COMPACT_ROWS * stage_ld);
+          compact = false;
+          mc = ms;
+        }
       }
     }
+    // trailing update A <- A - Lp^T Lp on the block-lower part: strip [c0, c1) from its first row down
+    for (int c0 = 0; c0 < ms; c0 += SW) {
+      const int c1 = c0 + SW < ms ? c0 + SW : ms;
+      int rc = gemm_rm(h, 'T', 'N', ms - c0, c1 - c0, nb, -1.0, d_Lp + c0, ldL, d_Lp + c0, ldL, 1.0,
+                       d_A + (int64_t)c0 * ldA + c0, ldA);
+      if (rc != ISDF_OK) return rc;
+    }
+    if (mc == 0 || mc == ms) continue;
+    std::vector<int32_t> cm(mc);
+    for (int i = 0; i < mc; ++i) cm[i] = cmap_h.empty() ? map_h[i] : cmap_h[map_h[i]];
+    cmap_h.swap(cm);
+    int rc = piv_to_original(hst.rank);
+    if (rc) return rc;
+    cc = cc < 0 ? 0 : cc ^ 1;
+    HIP_TRY(h, hipMemcpyAsync(d_map, map_h.data(), sizeof(int32_t) * mc, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_cmap[cc], cmap_h.data(), sizeof(int32_t) * mc, hipMemcpyHostToDevice, h->stream));
+    {
+      // one profiler "launch" per compaction; bytes = gather read + staging write + staging read + store of the block-lower part
+      ProfScope ps(h, "gram_compact[byte]", 32.0 * 0.5 * (double)mc * mc, 1);
+      const int nwc = (int)cdiv(mc, TPB);
+      if (TPB == 64) hipLaunchKernelGGL(gram_compact_diag_kernel<64>, dim3(nwc), dim3(64), 0, h->stream, d_d[cur], d_map, mc, d_d[cur ^ 1], d_w[cur ^ 1]);
+      else if (TPB == 128) hipLaunchKernelGGL(gram_compact_diag_kernel<128>, dim3(nwc), dim3(128), 0, h->stream, d_d[cur], d_map, mc, d_d[cur ^ 1], d_w[cur ^ 1]);
+      else hipLaunchKernelGGL(gram_compact_diag_kernel<256>, dim3(nwc), dim3(256), 0, h->stream, d_d[cur], d_map, mc, d_d[cur ^ 1], d_w[cur ^ 1]);
+      KERNEL_CHECK(h);
+      for (int r0 = 0; r0 < mc; r0 += COMPACT_ROWS) {
+        const int nr = mc - r0 < COMPACT_ROWS ? mc - r0 : COMPACT_ROWS;
+        const int ncol = (r0 / SW + 1) * SW < mc ? (r0 / SW + 1) * SW : mc;   // widest row of the chunk (one strip)
+        const dim3 grid((unsigned)cdiv(ncol, 256), (unsigned)nr);
+        hipLaunchKernelGGL(gram_compact_gather_kernel, grid, dim3(256), 0, h->stream, d_A, ldA, d_map, mc, r0,
+                           (double*)stage.p, stage_ld);
+        hipLaunchKernelGGL(gram_compact_store_kernel, grid, dim3(256), 0, h->stream, (const double*)stage.p, stage_ld, mc,
+                           r0, d_A, ldA);
+      }
+      KERNEL_CHECK(h);
+    }
+    cur ^= 1;
+    ms = mc;
+    nwg = (int)cdiv(ms, TPB);
+    rank_at_compact = hst.rank;
+    // map_h and cmap_h are rewritten at the next compaction only, after at least one more synchronisation
   }
   GramState hst;
   HIP_TRY(h, hipMemcpyAsync(&hst, d_st, sizeof(GramState), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  int rc = piv_to_original(hst.rank);
+  if (rc) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   *rank = hst.rank;
   return ISDF_OK;
