@@ -339,10 +339,14 @@ def test_coulomb_W(be, mk):
                                        ((26, 14, 22), 2), ((5, 3, 2), 9), ((1, 4, 6), 3), ((17, 8, 8), 3), ((40, 40, 40), 33),
                                        ((6, 45, 50), 3), ((4, 27, 25), 5), ((3, 120, 120), 2), ((2, 128, 128), 1)])
 def test_own_fft_convolution_matches_oracle_and_hipfft(be, mesh, nrow):
-    """S4 through the hand-written five-pass FFT (fft_conv.hip: radices 4/2/3/5 and the generic 7/11/13 butterflies, odd and
-    even lengths, odd line counts, several tiles) against the oracle's complex FFT + .real on a triclinic lattice
-    (<= 1e-12 of the largest value) and against the hipFFT path of the same library (own_fft = 0); (17, 8, 8) has a prime
-    factor above 13 and must take the hipFFT fallback with the same answer."""
+    """S4 through the hand-written FFT (fft_conv.hip) against the oracle's complex FFT + .real on a triclinic lattice
+    (<= 1e-12 of the largest value) and against the hipFFT path of the same library (own_fft = 0).  Paths by mesh: under
+    own_fft = 2 the 2-3-5 smooth meshes ((12, 12, 12), (10, 9, 8), (16, 20, 24), (5, 3, 2), (1, 4, 6), (40, 40, 40), (6, 45, 50),
+    (4, 27, 25), (3, 120, 120) - the one pipelined plane kernel here -, (2, 128, 128)) take the three-pass PLANE form and under
+    own_fft = 1 the five-pass FAST form; (21, 21, 21), (11, 9, 7), (26, 14, 22) have a factor 7 / 11 / 13 and take the five-pass
+    GENERIC form under either; (17, 8, 8) has a prime factor above 13 and must take the hipFFT fallback with the same answer.
+    Odd and even lengths, odd line counts, several tiles.  The sweep over every length, axis, path and plane kernel, with the
+    path asserted from the profiling labels, is tests/test_gpu_fft_sweep.py."""
     rng = np.random.default_rng(sum(mesh) + nrow)
     a = np.array([[4.1, 0.3, -0.2], [0.5, 3.7, 0.4], [-0.3, 0.6, 4.4]])
     G = int(np.prod(mesh))

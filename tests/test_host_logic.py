@@ -167,3 +167,21 @@ def test_occupied_orbitals_of_a_density_matrix():
     assert df._occupied_orbitals(dm + np.triu(np.ones((nao, nao)), 1) * 1e-3) is None
     assert df._occupied_orbitals(dm + 1e-3j * (c.dot(c.T) > 0)) is None
     assert df._occupied_orbitals(np.eye(nao)) is None
+
+
+def test_fft_float_reciprocal_index_split_is_exact():
+    """The plane and FAST kernels of csrc/fft_conv.hip split a flat index c into (c / n, c % n) through a single-precision
+    reciprocal, ``l = (int)(((float)c + 0.5f) * inv_n)`` with ``inv_n = 1.0f / (float)n`` (the loads, separations and stores of
+    z_r2c_fast_kernel / z_c2r_fast_kernel, plane_fwd_kernel / plane_inv_kernel, their pipelined forms and plane_c2c_inv_kernel,
+    with n = n2, n2 / 2 + 1; the butterfly index of stage_inplace / stage_plane with n = the stage stride and the line count).
+    c stays below the real plane, 2 * PLANE_ENTRIES = 20480.  Evaluated here in IEEE single precision operation by operation,
+    as the kernel does: equal to c // n for every n in 2..1024 (a change of the rounding, of the + 0.5f or of the plane limit
+    that breaks this would scatter plane entries silently)."""
+    c = np.arange(2 * 10240, dtype=np.int64)
+    cf = c.astype(np.float32) + np.float32(0.5)
+    assert cf.dtype == np.float32
+    for n in range(2, 1025):
+        inv_n = np.float32(1.0) / np.float32(n)
+        split = (cf * inv_n).astype(np.int64)                  # (int) truncates; all values are positive
+        assert (cf * inv_n).dtype == np.float32
+        assert np.array_equal(split, c // n), (n, c[split != c // n][:5])
