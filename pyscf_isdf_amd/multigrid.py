@@ -1,4 +1,4 @@
-"""Multigrid J and LDA potential on MI355X, paired with the ISDF exchange.
+"""Multigrid J, XC potential and XC linear response on MI355X, paired with the ISDF exchange.
 
 Role of ``pyscf.pbc.dft.multigrid`` (multigrid.py:500-529 get_j_kpts, :531-678 _eval_rhoG, :838-935 _get_j_pass2, :1046-1150
 nr_rks, :1556-1570 get_rho, :1853-1902 MultiGridFFTDF): the density of a Gaussian basis does not need the dense FFT mesh
@@ -280,8 +280,53 @@ def _is_slater(xc_code):
     return code in ('LDA,', 'SLATER,', 'LDA_X,', 'LDA', 'SLATER', 'LDA_X')
 
 
+class _Planes:
+    """Row layout of one level's collocation buffer, and the two maps between matrices and that layout.
+
+    k-points: the buffer holds the periodic parts u_k (the Bloch phases cancel in the density and in the potential matrix) as
+    rows (Re dense | Im dense | Re sparse | Im sparse), so that the first 2 nH rows are the dense functions' real and
+    imaginary planes and the whole buffer is the level's function set - the complex contractions then ARE real rectangular
+    ones on stacked planes.  Gamma point: the same with the imaginary planes absent, rows (dense | sparse)."""
+
+    def __init__(self, lv, cplx):
+        nH, nL = lv.nH, lv.nT - lv.nH
+        self.nH = nH
+        self.n = 2 if cplx else 1                                   # planes per function
+        self.rows = self.n * lv.nT
+        self.dense = slice(0, self.n * nH)                          # the dense functions' planes lead the buffer
+        # (dense rows, sparse rows) of the real planes and of the imaginary ones
+        self.re = (slice(0, nH), slice(self.n * nH, self.n * nH + nL))
+        self.im = (slice(nH, 2 * nH), slice(2 * nH + nL, 2 * (nH + nL))) if cplx else None
+
+    def stack(self, D):
+        """The real matrix M with rho_t = A (M B), A = the dense planes, B = the buffer, for the Hermitian block D (nset, nH, nT):
+        rho_t = Re sum_h u_h sum_t D'_ht conj(u_t) with D' = [D_hh | 2 D_hl] ((l, h) pairs ride with (h, l): their products are
+        the conjugates), M = [[Re D', Im D'], [-Im D', Re D']] in the buffer's row order; M = D' without imaginary planes."""
+        nH = self.nH
+        D = D.copy()
+        D[:, :, nH:] *= 2.0
+        if self.im is None:
+            return np.ascontiguousarray(D)
+        M = np.empty((D.shape[0], 2 * nH, self.rows))
+        for rows, (P, Q) in ((self.re[0], (D.real, D.imag)), (self.im[0], (-D.imag, D.real))):   # rows Re u_h: [p, q]; rows Im u_h: [-q, p]
+            M[:, rows, self.re[0]] = P[:, :, :nH]
+            M[:, rows, self.im[0]] = Q[:, :, :nH]
+            M[:, rows, self.re[1]] = P[:, :, nH:]
+            M[:, rows, self.im[1]] = Q[:, :, nH:]
+        return M
+
+    def unstack(self, R):
+        """V (nH, nT) = conj(u_h) v u_t from the product R of the dense planes with all planes (host array)."""
+        if self.im is None:
+            return R
+        nH = self.nH
+        cre, cim = np.r_[self.re], np.r_[self.im]
+        # conj(a + ib) v (c + id) = (a v c + b v d) + i (a v d - b v c)
+        return (R[:nH][:, cre] + R[nH:][:, cim]) + 1j * (R[:nH][:, cim] - R[nH:][:, cre])
+
+
 class MultiGridFFTDF(ISDF):
-    """FFTDF-shaped object: J (and the LDA potential) through the level ladder, K through ISDF.
+    """FFTDF-shaped object: J (and the XC potential) through the level ladder, K through ISDF.
 
     ``build()`` plans the levels; the ISDF fit is built the first time K is asked for.  ``tasks`` is the ladder
     (list of Level), as in the reference's attribute of that name."""
@@ -293,7 +338,7 @@ class MultiGridFFTDF(ISDF):
         self.level_toll = LEVEL_TOLL      # fixed cost of a level in the planner's model, seconds
         self.split = 'cost'               # 'cost': the cost model decides; 'all': one level per distinct mesh (tests)
         self.ao_cache_fraction = 0.25     # level collocations are kept between the two passes while they fit this share of free HBM
-        self._level_cache = {}
+        self._level_cache = {}            # (level, components) -> Gamma-point collocation
         self._k_requested = False
 
     # ---- planning ----------------------------------------------------------------------------
@@ -319,361 +364,120 @@ class MultiGridFFTDF(ISDF):
         return ISDF.reset(self, cell)
 
     # ---- level collocation -------------------------------------------------------------------
-    def _level_ao(self, it, keep):
-        """(nT, G_t) collocation of level ``it`` (dense rows first) on its own mesh."""
-        hit = self._level_cache.get(it)
-        if hit is not None:
-            return hit
+    def _level_ao(self, it, kpt, ncomp, keep):
+        """(ncomp, rows, G_t padded) collocation of level ``it`` on its own mesh, rows as _Planes lays them out: the functions
+        (ncomp = 1) or the functions and their x, y, z derivatives (ncomp = 4; the reference's RHOG_HIGH_ORDER branch), at the
+        Gamma point (``kpt`` None, real) or the periodic parts at ``kpt``.  Gamma-point sets are kept for the next pass if ``keep``."""
+        if kpt is None:
+            hit = self._level_cache.get((it, ncomp))
+            if hit is not None:
+                return hit
         lv, be, cell = self.tasks[it], self.backend, self.cell
+        pl = _Planes(lv, kpt is not None)
         # rows padded with zeros to a multiple of 32 grid points: the potential integral then runs on the aligned MFMA kernel
         # (90^3 and 70^3 are not multiples of 32; the unaligned variant is a third slower)
-        aoT = be.zeros((lv.nT, -(-lv.ngrids // 32) * 32))
+        buf = be.zeros((ncomp, pl.rows, -(-lv.ngrids // 32) * 32))
         coords_soa = be.uniform_grid(lv.mesh, cell.lattice_vectors())
+        atm = np.asarray(cell._atm)
+        out = buf[0] if ncomp == 1 else buf            # the plain kernels fill (rows, G) planes, the deriv1 ones (4, rows, G)
         # two launches: the collocation kernel walks one atom's shells per workgroup and wants them contiguous in bas
         nb = lv.nbas_h
-        be.eval_ao(np.asarray(cell._atm), lv.bas[:nb], lv.env, lv.Ls, lv.rcut[:nb], coords_soa, aoT[:lv.nH])
+        parts = [(0, lv.bas[:nb], lv.rcut[:nb])]
         if lv.nT > lv.nH:
-            be.eval_ao(np.asarray(cell._atm), lv.bas[nb:], lv.env, lv.Ls, lv.rcut[nb:], coords_soa, aoT[lv.nH:])
+            parts.append((1, lv.bas[nb:], lv.rcut[nb:]))
+        for part, bas, rcut in parts:                  # dense shells, sparse shells
+            if kpt is None:
+                (be.eval_ao if ncomp == 1 else be.eval_ao_deriv1)(atm, bas, lv.env, lv.Ls, rcut, coords_soa, out[..., pl.re[part], :])
+            else:
+                (be.eval_ao_k if ncomp == 1 else be.eval_ao_k_deriv1)(atm, bas, lv.env, lv.Ls, rcut, kpt, True, coords_soa,
+                                                                     out[..., pl.re[part], :], out[..., pl.im[part], :])
         if keep:
-            self._level_cache[it] = aoT
-        return aoT
+            self._level_cache[(it, ncomp)] = buf
+        return buf
 
-    def _cache_plan(self):
-        need = sum(8 * lv.nT * lv.ngrids for lv in self.tasks)
-        return need <= self.ao_cache_fraction * self.backend.free_bytes() or bool(self._level_cache)
+    def _cache_plan(self, kpts, ncomp):
+        """Whether this pass keeps its collocations for the next one: Gamma-point sets only (k-point sets are made per k-point
+        and used once), while the ladder's ``ncomp``-component set fits the allowed share of the free memory or sets of that
+        kind are resident already."""
+        if kpts is not None:
+            return False
+        need = sum(8 * ncomp * lv.nT * lv.ngrids for lv in self.tasks)
+        return need <= self.ao_cache_fraction * self.backend.free_bytes() or any(nc == ncomp for _, nc in self._level_cache)
 
     # ---- the two passes ----------------------------------------------------------------------
     def _spectrum_size(self):
         m = [int(x) for x in self.mesh]
         return m[0] * m[1] * (m[2] // 2 + 1)
 
-    def _eval_rhoG(self, dms):
-        """Half spectrum (nset, gc) of the density on the dense mesh, integral-normalised (rho(G) = int rho e^{-iGr}) as the
-        reference's _eval_rhoG; ``dms`` (nset, nao, nao) real."""
-        be, cell = self.backend, self.cell
-        self.build_tasks()
-        dms = np.asarray(dms, dtype=np.float64)
-        dms = 0.5 * (dms + dms.transpose(0, 2, 1))            # real AOs: only the symmetric part of D reaches the density
-        nset = dms.shape[0]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        spec = be.zeros((nset, self._spectrum_size()), dtype=torch.complex128)
-        keep = self._cache_plan()
-        for it, lv in enumerate(self.tasks):
-            aoT = self._level_ao(it, keep)
-            nH = lv.nH
-            idx_t = np.append(lv.idx_h, lv.idx_l)
-            D = dms[:, lv.idx_h[:, None], idx_t]                                     # (nset, nH, nT)
-            if len(lv.idx_l):
-                D[:, :, nH:] += dms[:, lv.idx_l[:, None], lv.idx_h].transpose(0, 2, 1)   # (l, h) pairs ride with (h, l)
-            rho = be.empty((nset, lv.ngrids))
-            be.rho_pair(aoT[:nH], aoT, lv.ngrids, be.to_device(np.ascontiguousarray(D)), rho)
-            be.mg_embed_density(rho, lv.mesh, cell.vol / lv.ngrids, spec, mesh, accumulate=True)
-            del rho, aoT
-        return spec
-
-    def _integrate(self, vspec):
-        """(nset, nao, nao) matrix of a potential given by its half spectrum on the dense mesh (role of _get_j_pass2)."""
-        be, cell = self.backend, self.cell
-        nao = cell.nao_nr()
-        nset = vspec.shape[0]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        out = np.zeros((nset, nao, nao))
-        keep = self._cache_plan()
-        for it, lv in enumerate(self.tasks):
-            aoT = self._level_ao(it, keep)
-            nH = lv.nH
-            v = be.empty((nset, lv.ngrids))
-            be.mg_restrict_potential(vspec, mesh, lv.mesh, 1.0 / lv.ngrids, v)
-            V = be.empty((nH, lv.nT))
-            vpad = be.zeros((aoT.shape[1],))
-            for i in range(nset):
-                vpad[:lv.ngrids].copy_(v[i])
-                be.gemm_nt(aoT[:nH], aoT, V, kscale=vpad)
-                Vh = be.to_host(V)
-                out[i][lv.idx_h[:, None], lv.idx_h] += Vh[:, :nH]
-                if len(lv.idx_l):
-                    out[i][lv.idx_h[:, None], lv.idx_l] += Vh[:, nH:]
-                    out[i][lv.idx_l[:, None], lv.idx_h] += Vh[:, nH:].T
-            del v, V, vpad, aoT
-        return out
-
-    # ---- GGA: densities and potentials with real-space gradients on every level (the reference's RHOG_HIGH_ORDER branch) ----
-    def _level_ao4(self, it, keep):
-        """(4, nT, G_t padded): values and x, y, z derivatives of level ``it``'s functions (dense rows first)."""
-        hit = self._level_cache.get((it, 'd1'))
-        if hit is not None:
-            return hit
-        lv, be, cell = self.tasks[it], self.backend, self.cell
-        ao4 = be.zeros((4, lv.nT, -(-lv.ngrids // 32) * 32))
-        coords_soa = be.uniform_grid(lv.mesh, cell.lattice_vectors())
-        nb = lv.nbas_h
-        atm = np.asarray(cell._atm)
-        be.eval_ao_deriv1(atm, lv.bas[:nb], lv.env, lv.Ls, lv.rcut[:nb], coords_soa, ao4[:, :lv.nH])
-        if lv.nT > lv.nH:
-            be.eval_ao_deriv1(atm, lv.bas[nb:], lv.env, lv.Ls, lv.rcut[nb:], coords_soa, ao4[:, lv.nH:])
-        if keep:
-            self._level_cache[(it, 'd1')] = ao4
-        return ao4
-
-    def _cache_plan_gga(self):
-        need = sum(32 * lv.nT * lv.ngrids for lv in self.tasks)
-        return need <= self.ao_cache_fraction * self.backend.free_bytes()
-
-    def _eval_rhoG_gga(self, dms):
-        """(4, nset, gc): half spectra of rho and of d rho / dx, dy, dz; the gradient of a level's density is taken in real space,
-        d_c rho_t = sum_h (d_c phi_h) (D' phi_T)_h + phi_h (D' d_c phi_T)_h  - two rectangular contractions per component."""
-        be, cell = self.backend, self.cell
-        self.build_tasks()
-        dms = np.asarray(dms, dtype=np.float64)
-        dms = 0.5 * (dms + dms.transpose(0, 2, 1))
-        nset = dms.shape[0]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        spec4 = be.zeros((4, nset, self._spectrum_size()), dtype=torch.complex128)
-        keep = self._cache_plan_gga()
-        for it, lv in enumerate(self.tasks):
-            ao4 = self._level_ao4(it, keep)
-            nH = lv.nH
-            idx_t = np.append(lv.idx_h, lv.idx_l)
-            D = dms[:, lv.idx_h[:, None], idx_t]
-            if len(lv.idx_l):
-                D[:, :, nH:] += dms[:, lv.idx_l[:, None], lv.idx_h].transpose(0, 2, 1)
-            d_D = be.to_device(np.ascontiguousarray(D))
-            rho = be.empty((nset, lv.ngrids))
-            w = cell.vol / lv.ngrids
-            be.rho_pair(ao4[0, :nH], ao4[0], lv.ngrids, d_D, rho)
-            be.mg_embed_density(rho, lv.mesh, w, spec4[0], mesh, accumulate=True)
-            for c in (1, 2, 3):
-                be.rho_pair(ao4[c, :nH], ao4[0], lv.ngrids, d_D, rho)
-                be.mg_embed_density(rho, lv.mesh, w, spec4[c], mesh, accumulate=True)
-                be.rho_pair(ao4[0, :nH], ao4[c], lv.ngrids, d_D, rho)
-                be.mg_embed_density(rho, lv.mesh, w, spec4[c], mesh, accumulate=True)
-            del rho, ao4
-        return spec4
-
-    def _integrate_gga(self, wspec4):
-        """(nset, nao, nao): sum_r [v0 phi_mu phi_nu + v_c d_c(phi_mu phi_nu)] for the potentials with spectra wspec4 (4, nset, gc)
-        (role of _get_gga_pass2, multigrid.py:936-1043): seven MFMA products per level, the potentials as per-k scales."""
-        be, cell = self.backend, self.cell
-        nao = cell.nao_nr()
-        nset = wspec4.shape[1]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        out = np.zeros((nset, nao, nao))
-        keep = self._cache_plan_gga()
-        for it, lv in enumerate(self.tasks):
-            ao4 = self._level_ao4(it, keep)
-            nH = lv.nH
-            v4 = be.empty((4, nset, lv.ngrids))
-            for c in range(4):
-                be.mg_restrict_potential(wspec4[c], mesh, lv.mesh, 1.0 / lv.ngrids, v4[c])
-            V = be.empty((nH, lv.nT))
-            vpad = be.zeros((ao4.shape[2],))
-            for i in range(nset):
-                vpad[:lv.ngrids].copy_(v4[0, i])
-                be.gemm_nt(ao4[0, :nH], ao4[0], V, kscale=vpad)
-                for c in (1, 2, 3):
-                    vpad[:lv.ngrids].copy_(v4[c, i])
-                    be.gemm_nt(ao4[0, :nH], ao4[c], V, beta=1.0, kscale=vpad)
-                    be.gemm_nt(ao4[c, :nH], ao4[0], V, beta=1.0, kscale=vpad)
-                Vh = be.to_host(V)
-                out[i][lv.idx_h[:, None], lv.idx_h] += Vh[:, :nH]
-                if len(lv.idx_l):
-                    out[i][lv.idx_h[:, None], lv.idx_l] += Vh[:, nH:]
-                    out[i][lv.idx_l[:, None], lv.idx_h] += Vh[:, nH:].T
-            del v4, V, vpad, ao4
-        return out
-
-    # ---- k-points: periodic parts u_k (the Bloch phases cancel in the density and in the potential matrix) ----------
-    def _level_ao_k(self, it, kpt):
-        """(2 nT, G_t) periodic parts of level ``it`` at ``kpt``: rows (Re dense | Im dense | Re sparse | Im sparse), so that the
-        first 2 nH rows are the dense functions' real and imaginary planes and the whole buffer is the level's function set -
-        the complex contractions then ARE the real rectangular ones of the Gamma point on stacked planes."""
-        lv, be, cell = self.tasks[it], self.backend, self.cell
-        nH, nL, nb = lv.nH, lv.nT - lv.nH, lv.nbas_h
-        buf = be.zeros((2 * lv.nT, -(-lv.ngrids // 32) * 32))
-        coords_soa = be.uniform_grid(lv.mesh, cell.lattice_vectors())
-        atm = np.asarray(cell._atm)
-        be.eval_ao_k(atm, lv.bas[:nb], lv.env, lv.Ls, lv.rcut[:nb], kpt, True, coords_soa, buf[:nH], buf[nH:2 * nH])
-        if nL:
-            be.eval_ao_k(atm, lv.bas[nb:], lv.env, lv.Ls, lv.rcut[nb:], kpt, True, coords_soa, buf[2 * nH:2 * nH + nL],
-                         buf[2 * nH + nL:])
-        return buf
-
-    def _eval_rhoG_k(self, dms, kpts):
-        """Half spectrum (nset, gc) of rho = 1/nk sum_k sum_ij D^k_ij u^k_i conj(u^k_j) for HERMITIAN ``dms`` (nset, nk, nao, nao):
-        rho_t = Re sum_h u_h sum_t D'_ht conj(u_t) with D' = [D_hh | 2 D_hl] (the (l,h) products are the conjugates of (h,l))
-        = A (M B) on the stacked planes A = (Re u_H; Im u_H), B = the level buffer, M = [[Re D', Im D'], [-Im D', Re D']]."""
+    def _eval_rhoG(self, dms, kpts=None, ncomp=1):
+        """Half spectra (ncomp, nset, gc) on the dense mesh, integral-normalised (rho(G) = int rho e^{-iGr}) as the reference's
+        _eval_rhoG, of rho = 1/nk sum_k sum_ij D^k_ij u^k_i conj(u^k_j) and, with ncomp = 4, of d rho / dx, dy, dz, for HERMITIAN
+        ``dms`` (nset, nk, nao, nao); ``kpts`` None: the Gamma point, nk = 1 and ``dms`` real symmetric.  The gradient of a level's
+        density is taken in real space, d_c rho_t = sum_h (d_c phi_h) (D' phi_T)_h + phi_h (D' d_c phi_T)_h - two rectangular
+        contractions per component."""
         be, cell = self.backend, self.cell
         self.build_tasks()
         nset, nk = dms.shape[:2]
         mesh = np.asarray(self.mesh, dtype=np.int32)
-        spec = be.zeros((nset, self._spectrum_size()), dtype=torch.complex128)
+        spec = be.zeros((ncomp, nset, self._spectrum_size()), dtype=torch.complex128)
+        keep = self._cache_plan(kpts, ncomp)
         for it, lv in enumerate(self.tasks):
-            nH, nL = lv.nH, lv.nT - lv.nH
-            idx_t = np.append(lv.idx_h, lv.idx_l)
-            rho = be.empty((nset, lv.ngrids))
-            for k in range(nk):
-                buf = self._level_ao_k(it, kpts[k])
-                D = dms[:, k][:, lv.idx_h[:, None], idx_t]                        # (nset, nH, nT) complex
-                D[:, :, nH:] *= 2.0
-                M = np.empty((nset, 2 * nH, 2 * lv.nT))
-                for r0, (P, Q) in ((0, (D.real, D.imag)), (nH, (-D.imag, D.real))):   # rows Re u_h: [p, q]; rows Im u_h: [-q, p]
-                    M[:, r0:r0 + nH, 0:nH] = P[:, :, :nH]
-                    M[:, r0:r0 + nH, nH:2 * nH] = Q[:, :, :nH]
-                    M[:, r0:r0 + nH, 2 * nH:2 * nH + nL] = P[:, :, nH:]
-                    M[:, r0:r0 + nH, 2 * nH + nL:] = Q[:, :, nH:]
-                be.rho_pair(buf[:2 * nH], buf, lv.ngrids, be.to_device(M), rho)
-                be.mg_embed_density(rho, lv.mesh, cell.vol / lv.ngrids / nk, spec, mesh, accumulate=True)
-                del buf
-        return spec
-
-    def _integrate_k(self, vspec, kpts_band):
-        """(nset, nband, nao, nao) complex matrices conj(u_i) v u_j of a real potential given by its half spectrum."""
-        be, cell = self.backend, self.cell
-        nao = cell.nao_nr()
-        nset = vspec.shape[0]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        out = np.zeros((nset, len(kpts_band), nao, nao), dtype=np.complex128)
-        for it, lv in enumerate(self.tasks):
-            nH, nL = lv.nH, lv.nT - lv.nH
-            v = be.empty((nset, lv.ngrids))
-            be.mg_restrict_potential(vspec, mesh, lv.mesh, 1.0 / lv.ngrids, v)
-            cre = np.r_[0:nH, 2 * nH:2 * nH + nL]
-            cim = np.r_[nH:2 * nH, 2 * nH + nL:2 * lv.nT]
-            for ib, kb in enumerate(kpts_band):
-                buf = self._level_ao_k(it, kb)
-                R = be.empty((2 * nH, 2 * lv.nT))
-                vpad = be.zeros((buf.shape[1],))
-                for i in range(nset):
-                    vpad[:lv.ngrids].copy_(v[i])
-                    be.gemm_nt(buf[:2 * nH], buf, R, kscale=vpad)
-                    Rh = be.to_host(R)
-                    # conj(a + ib) v (c + id) = (a v c + b v d) + i (a v d - b v c)
-                    V = (Rh[:nH][:, cre] + Rh[nH:][:, cim]) + 1j * (Rh[:nH][:, cim] - Rh[nH:][:, cre])
-                    out[i, ib][lv.idx_h[:, None], lv.idx_h] += V[:, :nH]
-                    if nL:
-                        out[i, ib][lv.idx_h[:, None], lv.idx_l] += V[:, nH:]
-                        out[i, ib][lv.idx_l[:, None], lv.idx_h] += V[:, nH:].conj().T
-                del buf, R, vpad
-            del v
-        return out
-
-    def _level_ao4_k(self, it, kpt):
-        """(4, 2 nT, G_t padded): values and derivatives of level ``it``'s functions at ``kpt`` (times exp(-i k.r)), every
-        component with the stacked rows (Re dense | Im dense | Re sparse | Im sparse) of _level_ao_k."""
-        lv, be, cell = self.tasks[it], self.backend, self.cell
-        nH, nL, nb = lv.nH, lv.nT - lv.nH, lv.nbas_h
-        buf = be.zeros((4, 2 * lv.nT, -(-lv.ngrids // 32) * 32))
-        coords_soa = be.uniform_grid(lv.mesh, cell.lattice_vectors())
-        atm = np.asarray(cell._atm)
-        be.eval_ao_k_deriv1(atm, lv.bas[:nb], lv.env, lv.Ls, lv.rcut[:nb], kpt, True, coords_soa, buf[:, :nH], buf[:, nH:2 * nH])
-        if nL:
-            be.eval_ao_k_deriv1(atm, lv.bas[nb:], lv.env, lv.Ls, lv.rcut[nb:], kpt, True, coords_soa,
-                                buf[:, 2 * nH:2 * nH + nL], buf[:, 2 * nH + nL:])
-        return buf
-
-    @staticmethod
-    def _stacked_dm(D, nH, nL):
-        """[[Re D', Im D'], [-Im D', Re D']] in the row / column order of the stacked planes, D' = D with its sparse columns
-        doubled; D (nset, nH, nH + nL) complex."""
-        D = D.copy()
-        D[:, :, nH:] *= 2.0
-        M = np.empty((D.shape[0], 2 * nH, 2 * (nH + nL)))
-        for r0, (P, Q) in ((0, (D.real, D.imag)), (nH, (-D.imag, D.real))):
-            M[:, r0:r0 + nH, 0:nH] = P[:, :, :nH]
-            M[:, r0:r0 + nH, nH:2 * nH] = Q[:, :, :nH]
-            M[:, r0:r0 + nH, 2 * nH:2 * nH + nL] = P[:, :, nH:]
-            M[:, r0:r0 + nH, 2 * nH + nL:] = Q[:, :, nH:]
-        return M
-
-    def _eval_rhoG_gga_k(self, dms, kpts):
-        """(4, nset, gc): spectra of rho and grad rho for Hermitian k-point matrices - _eval_rhoG_gga on the stacked planes."""
-        be, cell = self.backend, self.cell
-        self.build_tasks()
-        nset, nk = dms.shape[:2]
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        spec4 = be.zeros((4, nset, self._spectrum_size()), dtype=torch.complex128)
-        for it, lv in enumerate(self.tasks):
-            nH, nL = lv.nH, lv.nT - lv.nH
+            pl = _Planes(lv, kpts is not None)
             idx_t = np.append(lv.idx_h, lv.idx_l)
             rho = be.empty((nset, lv.ngrids))
             w = cell.vol / lv.ngrids / nk
-            for k in range(nk):
-                buf = self._level_ao4_k(it, kpts[k])
-                d_M = be.to_device(self._stacked_dm(dms[:, k][:, lv.idx_h[:, None], idx_t], nH, nL))
-                be.rho_pair(buf[0, :2 * nH], buf[0], lv.ngrids, d_M, rho)
-                be.mg_embed_density(rho, lv.mesh, w, spec4[0], mesh, accumulate=True)
-                for c in (1, 2, 3):
-                    be.rho_pair(buf[c, :2 * nH], buf[0], lv.ngrids, d_M, rho)
-                    be.mg_embed_density(rho, lv.mesh, w, spec4[c], mesh, accumulate=True)
-                    be.rho_pair(buf[0, :2 * nH], buf[c], lv.ngrids, d_M, rho)
-                    be.mg_embed_density(rho, lv.mesh, w, spec4[c], mesh, accumulate=True)
-                del buf
-        return spec4
+            for k, kpt in enumerate([None] if kpts is None else kpts):
+                ao = self._level_ao(it, kpt, ncomp, keep)
+                d_M = be.to_device(pl.stack(dms[:, k][:, lv.idx_h[:, None], idx_t]))      # from D (nset, nH, nT)
+                be.rho_pair(ao[0, pl.dense], ao[0], lv.ngrids, d_M, rho)
+                be.mg_embed_density(rho, lv.mesh, w, spec[0], mesh, accumulate=True)
+                for c in range(1, ncomp):
+                    be.rho_pair(ao[c, pl.dense], ao[0], lv.ngrids, d_M, rho)
+                    be.mg_embed_density(rho, lv.mesh, w, spec[c], mesh, accumulate=True)
+                    be.rho_pair(ao[0, pl.dense], ao[c], lv.ngrids, d_M, rho)
+                    be.mg_embed_density(rho, lv.mesh, w, spec[c], mesh, accumulate=True)
+                del ao
+        return spec
 
-    def _integrate_gga_k(self, wspec4, kpts_band):
-        """(nset, nband, nao, nao) complex: conj(u_i) [v0 u_j + v_c d_c u_j] + conj(d_c u_i) v_c u_j, seven real products per level
-        and k-point on the stacked planes, combined once."""
+    def _integrate(self, wspec, kpts_band=None):
+        """(nset, nband, nao, nao) matrices sum_r conj(u_i) [v0 u_j + v_c d_c u_j] + conj(d_c u_i) v_c u_j of the real potentials
+        given by their half spectra ``wspec`` (ncomp, nset, gc) on the dense mesh (role of _get_j_pass2 and, with ncomp = 4, of
+        _get_gga_pass2, multigrid.py:936-1043): one MFMA product per level and k-point, or seven, with the potentials as per-k
+        scales, on the stacked planes and combined once.  ``kpts_band`` None: the Gamma point, nband = 1 and a real result."""
         be, cell = self.backend, self.cell
         nao = cell.nao_nr()
-        nset = wspec4.shape[1]
+        ncomp, nset = wspec.shape[:2]
         mesh = np.asarray(self.mesh, dtype=np.int32)
-        out = np.zeros((nset, len(kpts_band), nao, nao), dtype=np.complex128)
+        band = [None] if kpts_band is None else kpts_band
+        out = np.zeros((nset, len(band), nao, nao), dtype=np.float64 if kpts_band is None else np.complex128)
+        keep = self._cache_plan(kpts_band, ncomp)
         for it, lv in enumerate(self.tasks):
-            nH, nL = lv.nH, lv.nT - lv.nH
-            v4 = be.empty((4, nset, lv.ngrids))
-            for c in range(4):
-                be.mg_restrict_potential(wspec4[c], mesh, lv.mesh, 1.0 / lv.ngrids, v4[c])
-            cre = np.r_[0:nH, 2 * nH:2 * nH + nL]
-            cim = np.r_[nH:2 * nH, 2 * nH + nL:2 * lv.nT]
-            for ib, kb in enumerate(kpts_band):
-                buf = self._level_ao4_k(it, kb)
-                R = be.empty((2 * nH, 2 * lv.nT))
-                vpad = be.zeros((buf.shape[2],))
+            pl = _Planes(lv, kpts_band is not None)
+            nH = lv.nH
+            v = be.empty((ncomp, nset, lv.ngrids))
+            for c in range(ncomp):
+                be.mg_restrict_potential(wspec[c], mesh, lv.mesh, 1.0 / lv.ngrids, v[c])
+            for ib, kb in enumerate(band):
+                ao = self._level_ao(it, kb, ncomp, keep)
+                R = be.empty((pl.n * nH, pl.rows))
+                vpad = be.zeros((ao.shape[2],))
                 for i in range(nset):
-                    vpad[:lv.ngrids].copy_(v4[0, i])
-                    be.gemm_nt(buf[0, :2 * nH], buf[0], R, kscale=vpad)
-                    for c in (1, 2, 3):
-                        vpad[:lv.ngrids].copy_(v4[c, i])
-                        be.gemm_nt(buf[0, :2 * nH], buf[c], R, beta=1.0, kscale=vpad)
-                        be.gemm_nt(buf[c, :2 * nH], buf[0], R, beta=1.0, kscale=vpad)
-                    Rh = be.to_host(R)
-                    V = (Rh[:nH][:, cre] + Rh[nH:][:, cim]) + 1j * (Rh[:nH][:, cim] - Rh[nH:][:, cre])
+                    vpad[:lv.ngrids].copy_(v[0, i])
+                    be.gemm_nt(ao[0, pl.dense], ao[0], R, kscale=vpad)
+                    for c in range(1, ncomp):
+                        vpad[:lv.ngrids].copy_(v[c, i])
+                        be.gemm_nt(ao[0, pl.dense], ao[c], R, beta=1.0, kscale=vpad)
+                        be.gemm_nt(ao[c, pl.dense], ao[0], R, beta=1.0, kscale=vpad)
+                    V = pl.unstack(be.to_host(R))
                     out[i, ib][lv.idx_h[:, None], lv.idx_h] += V[:, :nH]
-                    if nL:
+                    if len(lv.idx_l):
                         out[i, ib][lv.idx_h[:, None], lv.idx_l] += V[:, nH:]
                         out[i, ib][lv.idx_l[:, None], lv.idx_h] += V[:, nH:].conj().T
-                del buf, R, vpad
-            del v4
+                del ao, R, vpad
+            del v
         return out
 
-    def _hermitian_parts(self, dms):
-        """D = H + i A with H, A Hermitian: the density of D is rho(H) + i rho(A), both real (fft_jk.py:63-72 builds a complex
-        density for hermi = 0; J is linear, so the two real densities go through the ladder one after the other)."""
-        H = 0.5 * (dms + dms.conj().transpose(0, 1, 3, 2))
-        A = -0.5j * (dms - dms.conj().transpose(0, 1, 3, 2))
-        parts = [(1.0, H)]
-        if abs(A).max() > 1e-10:
-            parts.append((1j, A))
-        return parts
-
-    def get_j_kpts(self, dm_kpts, hermi=1, kpts=None, kpts_band=None):
-        """k-point J through the level ladder (multigrid.py:500-529); shapes as df_jk._format_jks (df_jk.py:1426-1444)."""
-        kpts = np.asarray(self.kpts if kpts is None else kpts, dtype=float).reshape(-1, 3)
-        nk, nao = len(kpts), self.cell.nao_nr()
-        dm_in = np.asarray(dm_kpts)
-        dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, nk, nao, nao)
-        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
-        band = kpts if band_in is None else band_in.reshape(-1, 3)
-        out_shape = dm_in.shape if band_in is None else \
-            (dm_in.shape[:-3] + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
-        be = self.backend
-        vj = np.zeros((dms.shape[0], len(band), nao, nao), dtype=np.complex128)
-        for fac, part in self._hermitian_parts(dms):
-            spec = self._eval_rhoG_k(part, kpts)
-            be.mg_coulomb_kernel(spec, np.asarray(self.mesh, dtype=np.int32), self.cell.lattice_vectors())
-            vj += fac * self._integrate_k(spec, band)
-        return vj.reshape(out_shape)
-
+    # ---- matrices in, matrices out -----------------------------------------------------------
     def _real_dms(self, dm):
         dm_in = np.asarray(dm)
         nao = self.cell.nao_nr()
@@ -681,24 +485,59 @@ class MultiGridFFTDF(ISDF):
             raise NotImplementedError('multigrid J at the Gamma point takes real density matrices')
         return dm_in.shape, np.ascontiguousarray(dm_in.real.reshape(-1, nao, nao), dtype=np.float64)
 
+    def _format_dms(self, dm, kpts, kpts_band=None):
+        """(dms (nset, nk, nao, nao), kpts, band k-points, shape of the result) for the two passes.  ``kpts`` None: the Gamma
+        point - real matrices, kpts and band None, the result shaped like ``dm``; else complex matrices, kpts (nk, 3), and the
+        result on kpts or on kpts_band, shaped as df_jk._format_jks shapes it (df_jk.py:1426-1444)."""
+        if kpts is None:
+            shape, dms = self._real_dms(dm)
+            return dms[:, None], None, None, shape
+        kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
+        nao = self.cell.nao_nr()
+        dm_in = np.asarray(dm)
+        dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
+        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
+        band = kpts if band_in is None else band_in.reshape(-1, 3)
+        shape = dm_in.shape if band_in is None else (dm_in.shape[:-3] + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
+        return dms, kpts, band, shape
+
+    def _hermitian_parts(self, dms, anti=True):
+        """D = H + i A with H, A Hermitian: the density of D is rho(H) + i rho(A), both real (fft_jk.py:63-72 builds a complex
+        density for hermi = 0; J is linear, so the two real densities go through the ladder one after the other).  Returns
+        [(1, H)] and, if ``anti`` and A is there, (i, A).  Real matrices (the Gamma point, real functions): only the symmetric part
+        of D reaches the density."""
+        H = 0.5 * (dms + dms.conj().transpose(0, 1, 3, 2))
+        parts = [(1.0, H)]
+        if anti and np.iscomplexobj(dms):
+            A = -0.5j * (dms - dms.conj().transpose(0, 1, 3, 2))
+            if abs(A).max() > 1e-10:
+                parts.append((1j, A))
+        return parts
+
+    def _get_j(self, dm, kpts, kpts_band=None):
+        dms, kpts, band, shape = self._format_dms(dm, kpts, kpts_band)
+        vj = 0.0
+        for fac, part in self._hermitian_parts(dms):
+            spec = self._eval_rhoG(part, kpts)
+            self.backend.mg_coulomb_kernel(spec[0], np.asarray(self.mesh, dtype=np.int32), self.cell.lattice_vectors())
+            vj = vj + fac * self._integrate(spec, band)
+        return vj.reshape(shape)
+
+    def get_j_kpts(self, dm_kpts, hermi=1, kpts=None, kpts_band=None):
+        """k-point J through the level ladder (multigrid.py:500-529); shapes as df_jk._format_jks."""
+        return self._get_j(dm_kpts, self.kpts if kpts is None else kpts, kpts_band)
+
     def get_j(self, dm):
         """J of the Gamma-point density matrix (or stack of them) through the level ladder."""
-        shape, dms = self._real_dms(dm)
-        spec = self._eval_rhoG(dms)
-        self.backend.mg_coulomb_kernel(spec, np.asarray(self.mesh, dtype=np.int32), self.cell.lattice_vectors())
-        return self._integrate(spec).reshape(shape)
+        return self._get_j(dm, None)
 
     def get_rho(self, dm, kpts=None):
         """Density on the dense mesh (multigrid.py:1556-1570)."""
         if kpts is not None and not self._is_gamma(kpts):
             raise NotImplementedError('multigrid get_rho is implemented at the Gamma point')
-        _, dms = self._real_dms(dm)
-        be = self.backend
-        spec = self._eval_rhoG(dms)
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        rho = be.empty((dms.shape[0], int(np.prod(mesh))))
-        be.mg_restrict_potential(spec, mesh, mesh, 1.0 / self.cell.vol, rho)
-        out = be.to_host(rho)
+        dms = self._format_dms(dm, None)[0]
+        spec = self._eval_rhoG(self._hermitian_parts(dms)[0][1])
+        out = self.backend.to_host(_real_space(self, spec, 1.0 / self.cell.vol)[0])
         return out[0] if np.asarray(dm).ndim == 2 else out
 
     # ---- FFTDF surface -----------------------------------------------------------------------
@@ -710,19 +549,11 @@ class MultiGridFFTDF(ISDF):
             # range separation: the parent's J with the attenuated kernel (dense mesh) and its own W; not a multigrid case
             self._k_requested = True
             return ISDF.get_jk(self, dm, hermi, kpts, kpts_band, with_j, with_k, omega, exxdiv)
-        if not gamma:
-            vj = vk = None
-            if with_j:
-                vj = self.get_j_kpts(dm, hermi, kpts, kpts_band)
-            if with_k:
-                self._k_requested = True      # the k-point fit lives in the parent's build
-                vk = ISDF.get_jk(self, dm, hermi, kpts, kpts_band, False, True, omega, exxdiv)[1]
-            return vj, vk
         vj = vk = None
         if with_j:
-            vj = self.get_j(dm)
+            vj = self.get_j(dm) if gamma else self.get_j_kpts(dm, hermi, kpts, kpts_band)
         if with_k:
-            self._k_requested = True
+            self._k_requested = True      # the fit (Gamma point or k-points) lives in the parent's build
             vk = ISDF.get_jk(self, dm, hermi, kpts, kpts_band, False, True, omega, exxdiv)[1]
         return vj, vk
 
@@ -735,258 +566,169 @@ def get_j_kpts(mydf, dm_kpts, hermi=1, kpts=np.zeros((1, 3)), kpts_band=None):
     return mydf.get_j_kpts(dm_kpts, hermi, kpts, kpts_band)
 
 
-def nr_rks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
-    """XC energy and potential matrix of a closed-shell density through the level ladder (multigrid.py:1046-1150), Slater
-    exchange; Gamma point (real matrices) or k-points (dm (nk, nao, nao) or (nset, nk, nao, nao), complex result on the
-    k-points or on kpts_band).  Returns (nelec, exc, veff) with veff tagged ecoul / exc / vj / vk like the reference's; with_j
-    adds the Coulomb potential to veff before the integration pass (one pass for J + XC)."""
-    kind = _xc_kind(xc_code)
-    if kind is None:
-        raise NotImplementedError("xc=%r: 'lda,' (Slater exchange), 'lda,vwn' (+ VWN5 correlation) and 'b88,' (Becke-88 exchange) are "
-                                  "implemented (no libxc in this tree)" % (xc_code,))
+def _real_space(mydf, spec, scale):
+    """scale * the real fields (ncomp, nset, G) on the dense mesh of the half spectra ``spec`` (ncomp, nset, gc)."""
+    be = mydf.backend
+    mesh = np.asarray(mydf.mesh, dtype=np.int32)
+    out = be.empty(tuple(spec.shape[:2]) + (int(np.prod(mesh)),))
+    for c in range(spec.shape[0]):
+        be.mg_restrict_potential(spec[c], mesh, mesh, scale, out[c])
+    return out
+
+
+def _ncomp(kind):
+    """Components the ladder carries for a functional: the density, or (a GGA) the density and its gradient."""
+    return 4 if kind == 'b88' else 1
+
+
+def _kpts_or_gamma(mydf, kpts, kpts_band):
+    """None where the Gamma-point layout (real matrices) serves, else the k-points; ``kpts`` None: those of ``mydf``."""
     if kpts is None:
         kpts = mydf.kpts
-    be, cell = mydf.backend, mydf.cell
-    gamma = mydf._is_gamma(kpts) and mydf._is_gamma(kpts_band)
-    nao = cell.nao_nr()
-    if kind == 'b88':
-        return _nr_rks_gga(mydf, dm_kpts, with_j, return_j, None if gamma else kpts, kpts_band)
-    if gamma:
-        shape, dms = mydf._real_dms(dm_kpts)
-        spec = mydf._eval_rhoG(dms)
-
-        def integrate(sp):
-            return mydf._integrate(sp).reshape(shape)
-    else:
-        kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-        dm_in = np.asarray(dm_kpts)
-        dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
-        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
-        band = kpts if band_in is None else band_in.reshape(-1, 3)
-        shape = dm_in.shape if band_in is None else (dm_in.shape[:-3] + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
-        # the XC functional sees the real density: the Hermitian part of D (the reference takes the real part of rho)
-        spec = mydf._eval_rhoG_k(0.5 * (dms + dms.conj().transpose(0, 1, 3, 2)), kpts)
-
-        def integrate(sp):
-            return mydf._integrate_k(sp, band).reshape(shape)
-    nset = dms.shape[0]
-    mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    G = int(np.prod(mesh))
-    weight = cell.vol / G
-    rho = be.empty((nset, G))
-    be.mg_restrict_potential(spec, mesh, mesh, 1.0 / cell.vol, rho)
-    be.mg_coulomb_kernel(spec, mesh, cell.lattice_vectors())                 # spec now holds the Hartree potential
-    vH = be.empty((nset, G))
-    be.mg_restrict_potential(spec, mesh, mesh, 1.0 / cell.vol, vH)
-    exc = be.empty((nset, G))
-    vxc = be.empty((nset, G))
-    nelec, excsum, ecoul = np.zeros(nset), np.zeros(nset), np.zeros(nset)
-    for i in range(nset):
-        be.lda_exchange(rho[i], exc[i], vxc[i])
-        if _has_vwn(xc_code):
-            be.lda_vwn_add(rho[i], exc[i], vxc[i])
-        nelec[i] = be.dot(rho[i]) * weight
-        excsum[i] = be.dot(rho[i], exc[i]) * weight
-        ecoul[i] = 0.5 * be.dot(rho[i], vH[i]) * weight
-    del exc, vH
-    vj = integrate(spec) if return_j else None
-    if not with_j:
-        spec.zero_()
-    be.mg_embed_density(vxc, mesh, weight, spec, mesh, accumulate=True)      # + spectrum of the XC potential
-    veff = integrate(spec)
-    if nset == 1:
-        nelec, excsum, ecoul = nelec[0], excsum[0], ecoul[0]
-    return nelec, excsum, TaggedArray(veff, ecoul=ecoul, exc=excsum, vj=vj, vk=None)
+    return None if mydf._is_gamma(kpts) and mydf._is_gamma(kpts_band) else kpts
 
 
-def _nr_rks_gga(mydf, dm, with_j, return_j, kpts=None, kpts_band=None):
-    """'b88,': rho and grad rho from the ladder (real-space gradients per level), the functional on the dense mesh (isdf_gga_b88),
-    the potential v_rho phi phi + (de/d grad rho) . grad(phi phi) back through the ladder; Gamma point (kpts None) or k-points."""
-    be, cell = mydf.backend, mydf.cell
-    nao = cell.nao_nr()
-    if kpts is None:
-        shape, dms = mydf._real_dms(dm)
-        spec4 = mydf._eval_rhoG_gga(dms)
-        integrate_lda = lambda sp: mydf._integrate(sp).reshape(shape)            # noqa: E731
-        integrate_gga = lambda sp4: mydf._integrate_gga(sp4).reshape(shape)      # noqa: E731
-    else:
-        kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-        dm_in = np.asarray(dm)
-        dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
-        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
-        band = kpts if band_in is None else band_in.reshape(-1, 3)
-        shape = dm_in.shape if band_in is None else (dm_in.shape[:-3] + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
-        spec4 = mydf._eval_rhoG_gga_k(0.5 * (dms + dms.conj().transpose(0, 1, 3, 2)), kpts)
-        integrate_lda = lambda sp: mydf._integrate_k(sp, band).reshape(shape)    # noqa: E731
-        integrate_gga = lambda sp4: mydf._integrate_gga_k(sp4, band).reshape(shape)   # noqa: E731
-    nset = dms.shape[0]
-    mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    G = int(np.prod(mesh))
-    weight = cell.vol / G
-    rho4 = be.empty((4, nset, G))
-    for c in range(4):
-        be.mg_restrict_potential(spec4[c], mesh, mesh, 1.0 / cell.vol, rho4[c])
-    vHspec = spec4[0].clone()
-    be.mg_coulomb_kernel(vHspec, mesh, cell.lattice_vectors())
-    vH = be.empty((nset, G))
-    be.mg_restrict_potential(vHspec, mesh, mesh, 1.0 / cell.vol, vH)
-    exc = be.empty((nset, G))
-    vrho = be.empty((nset, G))
-    w = be.empty((3, nset, G))
-    nelec, excsum, ecoul = np.zeros(nset), np.zeros(nset), np.zeros(nset)
-    for i in range(nset):
-        be.gga_b88(rho4[0, i], rho4[1:, i], exc[i], vrho[i], w[:, i])
-        nelec[i] = be.dot(rho4[0, i]) * weight
-        excsum[i] = be.dot(rho4[0, i], exc[i]) * weight
-        ecoul[i] = 0.5 * be.dot(rho4[0, i], vH[i]) * weight
-    del exc, vH, rho4
-    vj = integrate_lda(vHspec) if return_j else None
-    spec4.zero_()
-    if with_j:
-        spec4[0].copy_(vHspec)
-    be.mg_embed_density(vrho, mesh, weight, spec4[0], mesh, accumulate=True)
-    for c in range(3):
-        be.mg_embed_density(w[c], mesh, weight, spec4[1 + c], mesh, accumulate=True)
-    veff = integrate_gga(spec4)
-    if nset == 1:
-        nelec, excsum, ecoul = nelec[0], excsum[0], ecoul[0]
-    return nelec, excsum, TaggedArray(veff, ecoul=ecoul, exc=excsum, vj=vj, vk=None)
+def nr_rks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
+    """XC energy and potential matrix of a closed-shell density through the level ladder (multigrid.py:1046-1150): Slater
+    exchange (with or without VWN5 correlation) or Becke-88 exchange; Gamma point (real matrices) or k-points (dm (nk, nao, nao)
+    or (nset, nk, nao, nao), complex result on the k-points or on kpts_band).  Returns (nelec, exc, veff) with veff tagged
+    ecoul / exc / vj / vk like the reference's; with_j adds the Coulomb potential to veff before the integration pass (one pass
+    for J + XC)."""
+    if _xc_kind(xc_code) is None:
+        raise NotImplementedError("xc=%r: 'lda,' (Slater exchange), 'lda,vwn' (+ VWN5 correlation) and 'b88,' (Becke-88 exchange) are "
+                                  "implemented (no libxc in this tree)" % (xc_code,))
+    return _nr_ks(mydf, xc_code, dm_kpts, _kpts_or_gamma(mydf, kpts, kpts_band), kpts_band, with_j, return_j, False)
 
 
 def nr_uks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
     """Open-shell form (multigrid.py:1152-1257): dm = (alpha, beta), each (nao, nao) at the Gamma point or (nk, nao, nao) at
-    k-points.  Returns (nelec [both spins together], exc, veff (2, ...)); Slater exchange by spin scaling,
+    k-points.  Returns (nelec [both spins together], exc, veff (2, ...)); exchange functionals by spin scaling,
     E_x[rho_a, rho_b] = (E_x[2 rho_a] + E_x[2 rho_b]) / 2, v_a = v_x[2 rho_a]; the Coulomb potential of with_j is that of the
     total density."""
     if _has_vwn(xc_code):
         raise NotImplementedError("xc=%r: the spin-polarised VWN correlation is not implemented (closed-shell nr_rks only)" % (xc_code,))
-    kind = _xc_kind(xc_code)
-    if kind is None:
+    if _xc_kind(xc_code) is None:
         raise NotImplementedError("xc=%r: 'lda,' (Slater exchange) and 'b88,' (Becke-88 exchange) are implemented (no libxc in this "
                                   "tree)" % (xc_code,))
-    if kpts is None:
-        kpts = mydf.kpts
-    be, cell = mydf.backend, mydf.cell
-    gamma = mydf._is_gamma(kpts) and mydf._is_gamma(kpts_band)
-    nao = cell.nao_nr()
+    kpts = _kpts_or_gamma(mydf, kpts, kpts_band)
     dm_in = np.asarray(dm_kpts)
-    if dm_in.shape[0] != 2 or dm_in.ndim != (3 if gamma else 4):
+    if dm_in.shape[0] != 2 or dm_in.ndim != (3 if kpts is None else 4):
         raise ValueError('nr_uks takes one pair (alpha, beta) of density matrices')
-    if kind == 'b88':
-        return _nr_uks_gga(mydf, dm_in, with_j, return_j, None if gamma else kpts, kpts_band)
-    if gamma:
-        shape, dms = mydf._real_dms(dm_in)
-        spec = mydf._eval_rhoG(dms)
+    return _nr_ks(mydf, xc_code, dm_in, kpts, kpts_band, with_j, return_j, True)
 
-        def integrate(sp):
-            return mydf._integrate(sp).reshape(shape)
-    else:
-        kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-        dms = np.asarray(dm_in, dtype=np.complex128)
-        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
-        band = kpts if band_in is None else band_in.reshape(-1, 3)
-        shape = dm_in.shape if band_in is None else ((2,) + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
-        spec = mydf._eval_rhoG_k(0.5 * (dms + dms.conj().transpose(0, 1, 3, 2)), kpts)
 
-        def integrate(sp):
-            return mydf._integrate_k(sp, band).reshape(shape)
+def _nr_ks(mydf, xc_code, dm, kpts, kpts_band, with_j, return_j, spin):
+    """The Kohn-Sham pass pair behind nr_rks and nr_uks: rho (and grad rho for a GGA, real-space gradients per level) from the
+    ladder, the functional on the dense mesh (isdf_lda_exchange [+ isdf_lda_vwn_add] or isdf_gga_b88), the potential
+    v_rho phi phi + (de/d grad rho) . grad(phi phi) back through the ladder.  ``kpts`` None: the Gamma point.  ``spin``: dm is
+    the pair (alpha, beta) and each spin channel is the closed-shell functional at (2 rho_s, 2 grad rho_s) - potentials come out
+    as they are, energies halved - with the Hartree potential of the total density."""
+    be, cell = mydf.backend, mydf.cell
+    kind = _xc_kind(xc_code)
+    ncomp = _ncomp(kind)
+    dms, kpts, band, shape = mydf._format_dms(dm, kpts, kpts_band)
+    # the XC functional sees the real density: the Hermitian part of D (the reference takes the real part of rho)
+    spec = mydf._eval_rhoG(mydf._hermitian_parts(dms, anti=False)[0][1], kpts, ncomp)
+
+    def integrate(sp):
+        return mydf._integrate(sp, band).reshape(shape)
+    nset = dms.shape[0]
     mesh = np.asarray(mydf.mesh, dtype=np.int32)
     G = int(np.prod(mesh))
     weight = cell.vol / G
-    rho2 = be.empty((2, G))                                                  # 2 rho_sigma: what the spin-scaled functional sees
-    be.mg_restrict_potential(spec, mesh, mesh, 2.0 / cell.vol, rho2)
-    be.mg_coulomb_kernel(spec, mesh, cell.lattice_vectors())                 # spec rows: Hartree potentials of alpha and of beta
-    vH = be.empty((2, G))
-    be.mg_restrict_potential(spec, mesh, mesh, 1.0 / cell.vol, vH)
-    exc = be.empty((2, G))
-    vxc = be.empty((2, G))
-    nelec = excsum = ecoul = 0.0
-    for sp in range(2):
-        be.lda_exchange(rho2[sp], exc[sp], vxc[sp])
-        nelec += 0.5 * be.dot(rho2[sp]) * weight
-        excsum += 0.5 * be.dot(rho2[sp], exc[sp]) * weight
-        ecoul += 0.25 * (be.dot(rho2[sp], vH[0]) + be.dot(rho2[sp], vH[1])) * weight
-    vj = None
-    if return_j:
-        vj2 = integrate(spec)
-        vj = vj2[0] + vj2[1]
-    # veff_sigma = v_x[2 rho_sigma] (+ the Hartree potential of the total density): three real fields into each spin's spectrum
-    spec.zero_()
-    be.mg_embed_density(vxc, mesh, weight, spec, mesh, accumulate=True)
-    if with_j:
-        vtot = be.empty((2, G))
-        for sp in range(2):
-            vtot[sp].copy_(vH[1 - sp])
-        be.mg_embed_density(vH, mesh, weight, spec, mesh, accumulate=True)
-        be.mg_embed_density(vtot, mesh, weight, spec, mesh, accumulate=True)
+    scale = 2.0 if spin else 1.0                                             # 2 rho_sigma: what the spin-scaled functional sees
+    rho = _real_space(mydf, spec, scale / cell.vol)
+    be.mg_coulomb_kernel(spec[0], mesh, cell.lattice_vectors())              # spec[0] now holds the Hartree potentials, set by set
+    vH = _real_space(mydf, spec[:1], 1.0 / cell.vol)[0]
+    exc = be.empty((nset, G))
+    vxc = be.empty((ncomp, nset, G))                                         # v_rho and, for a GGA, de/d grad rho
+    nelec, excsum, ecoul = np.zeros(nset), np.zeros(nset), np.zeros(nset)
+    for i in range(nset):
+        if kind == 'b88':
+            be.gga_b88(rho[0, i], rho[1:, i], exc[i], vxc[0, i], vxc[1:, i])
+        else:
+            be.lda_exchange(rho[0, i], exc[i], vxc[0, i])
+            if _has_vwn(xc_code):
+                be.lda_vwn_add(rho[0, i], exc[i], vxc[0, i])
+        nelec[i] = be.dot(rho[0, i]) / scale * weight
+        excsum[i] = be.dot(rho[0, i], exc[i]) / scale * weight
+        # a spin's density meets the Hartree potential of both spins, a closed-shell density its own
+        ecoul[i] = 0.5 / scale * sum(be.dot(rho[0, i], vH[j]) for j in (range(nset) if spin else (i,))) * weight
+    del exc, rho
+    vj = integrate(spec[:1]) if return_j else None
+    # potential spectra: XC on every component; J stays where it is for a closed shell, and is added in real space for a pair
+    spec[1:].zero_()
+    if spin or not with_j:
+        spec[0].zero_()
+    for c in range(ncomp):
+        be.mg_embed_density(vxc[c], mesh, weight, spec[c], mesh, accumulate=True)
+    if spin:
+        nelec, excsum, ecoul = nelec.sum(), excsum.sum(), ecoul.sum()
+        if return_j:
+            vj = vj[0] + vj[1]
+        if with_j:                                                           # veff_sigma += the Hartree potential of the total density
+            vtot = be.empty((2, G))
+            for sp in range(2):
+                vtot[sp].copy_(vH[1 - sp])
+            be.mg_embed_density(vH, mesh, weight, spec[0], mesh, accumulate=True)
+            be.mg_embed_density(vtot, mesh, weight, spec[0], mesh, accumulate=True)
+    elif nset == 1:
+        nelec, excsum, ecoul = nelec[0], excsum[0], ecoul[0]
     veff = integrate(spec)
     return nelec, excsum, TaggedArray(veff, ecoul=ecoul, exc=excsum, vj=vj, vk=None)
 
 
 # ---- linear response of the XC potential (TDDFT / stability / Hessians), multigrid.py:1259-1550 ---------------------------
-def _density_passes(mydf, dm_in, kpts):
-    """What the response functions share: the spectra of the (real) densities a stack of matrices stands for, each with its
-    factor (Gamma: one pass; k-points: Hermitian and, if present, anti-Hermitian part), an integrator and the result shape."""
-    nao = mydf.cell.nao_nr()
-    dm_in = np.asarray(dm_in)
-    if kpts is None or mydf._is_gamma(kpts):
-        shape, dms = mydf._real_dms(dm_in)
-        return [(1.0, mydf._eval_rhoG(dms))], (lambda sp: mydf._integrate(sp).reshape(shape)), dms.shape[0]
-    kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-    dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
-    passes = [(fac, mydf._eval_rhoG_k(part, kpts)) for fac, part in mydf._hermitian_parts(dms)]
-    return passes, (lambda sp: mydf._integrate_k(sp, kpts).reshape(dm_in.shape)), dms.shape[0]
+def _density_passes(mydf, dm_in, kpts, ncomp=1):
+    """What the response functions share: the spectra (ncomp, nset, gc) of the (real) densities - with their gradients for
+    ncomp = 4 - a stack of matrices stands for, each with its factor (Gamma: one pass; k-points: Hermitian and, if present,
+    anti-Hermitian part), an integrator and nset."""
+    dms, kpts, band, shape = mydf._format_dms(dm_in, None if kpts is None or mydf._is_gamma(kpts) else kpts)
+    passes = [(fac, mydf._eval_rhoG(part, kpts, ncomp)) for fac, part in mydf._hermitian_parts(dms)]
+    return passes, (lambda sp: mydf._integrate(sp, band).reshape(shape)), dms.shape[0]
 
 
-def _real_space(mydf, spec, scale):
-    mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    out = mydf.backend.empty((spec.shape[0], int(np.prod(mesh))))
-    mydf.backend.mg_restrict_potential(spec, mesh, mesh, scale, out)
-    return out
-
-
-def _ground_density(mydf, dm0, kpts, scale=1.0):
-    """scale * rho of the ground-state matrix (or (alpha, beta) pair) on the dense mesh, device (nset, G)."""
-    passes, _, _ = _density_passes(mydf, dm0, kpts)
+def _ground_density(mydf, dm0, kpts, scale=1.0, ncomp=1):
+    """scale * rho (ncomp = 4: and grad rho) of the ground-state matrix (or (alpha, beta) pair) on the dense mesh, device
+    (ncomp, nset, G)."""
+    passes, _, _ = _density_passes(mydf, dm0, kpts, ncomp)
     return _real_space(mydf, passes[0][1], scale / mydf.cell.vol)
 
 
-def _response(mydf, dms, kpts, kernel_rows, with_j, total_j=False, w_scale=1.0, contract=None):
-    """veff[n] = matrix of  w_scale * kernel_rows[n] * rho1[n]  (+ Hartree potential of rho1[n], or of the pair's sum with total_j);
-    ``contract`` (rho1 (1, nset, G) -> w (1, nset, G)) replaces the row product for a caller-supplied kernel."""
+def _response(mydf, dms, kpts, contract, with_j, total_j=False, w_scale=1.0, ncomp=1):
+    """veff[n] = matrix of  w_scale * wv[n]  with wv = contract(rho1) (ncomp, nset, G), rho1 = the density (ncomp = 4: and its
+    gradient) of each response matrix (+ Hartree potential of rho1[n], or of the pair's sum with total_j, on component 0)."""
     be, cell = mydf.backend, mydf.cell
     mesh = np.asarray(mydf.mesh, dtype=np.int32)
     weight = cell.vol / int(np.prod(mesh))
-    passes, integrate, nset = _density_passes(mydf, dms, kpts)
+    passes, integrate, nset = _density_passes(mydf, dms, kpts, ncomp)
     veff = 0.0
     for fac, spec in passes:
-        w = _real_space(mydf, spec, 1.0 / cell.vol)                          # rho1 (nset, G)
-        if contract is not None:
-            w = contract(w[None])[0]
-        else:
-            for n in range(nset):
-                be.hadamard_rows(w[n:n + 1], kernel_rows[n:n + 1])
+        wv = contract(_real_space(mydf, spec, 1.0 / cell.vol))
         if with_j:
-            be.mg_coulomb_kernel(spec, mesh, cell.lattice_vectors())
+            be.mg_coulomb_kernel(spec[0], mesh, cell.lattice_vectors())
             if total_j:                                                      # both spins feel the Hartree potential of the sum
-                _add_partner_hartree(mydf, spec, nset)
+                _add_partner_hartree(mydf, spec[:1], nset)
         else:
-            spec.zero_()
-        be.mg_embed_density(w, mesh, weight * w_scale, spec, mesh, accumulate=True)
+            spec[0].zero_()
+        spec[1:].zero_()
+        for c in range(ncomp):
+            be.mg_embed_density(wv[c], mesh, weight * w_scale, spec[c], mesh, accumulate=True)
         veff = veff + fac * integrate(spec)
     return np.asarray(veff)
 
 
 def _add_partner_hartree(mydf, spec, nset):
-    """spec rows hold the Hartree potentials of (alpha responses | beta responses): add to each the one of its partner spin."""
+    """spec (1, nset, gc) holds the Hartree potentials of (alpha responses | beta responses): add to each the one of its partner
+    spin."""
     be, cell = mydf.backend, mydf.cell
     mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    vH = _real_space(mydf, spec, 1.0 / cell.vol)
+    vH = _real_space(mydf, spec, 1.0 / cell.vol)[0]
     swapped = be.empty(tuple(vH.shape))
     half = nset // 2
     swapped[:half].copy_(vH[half:])
     swapped[half:].copy_(vH[:half])
-    be.mg_embed_density(swapped, mesh, cell.vol / int(np.prod(mesh)), spec, mesh, accumulate=True)
+    be.mg_embed_density(swapped, mesh, cell.vol / int(np.prod(mesh)), spec[0], mesh, accumulate=True)
 
 
 def _response_kind(xc_code, open_shell=False):
@@ -1010,6 +752,7 @@ def _nset_of(mydf, dms, kpts):
     return int(np.asarray(dms).size // (nk * nao * nao))
 
 
+# ---- contract: rho1 (ncomp, nset, G) -> wv (ncomp, nset, G), the kernel applied to every response density ----------------------
 def _kernel_rows(mydf, rho0_dev, fxc, nrows, vwn=False):
     """Device rows f[n] = f_x(density row) (+ f_c of VWN5) (or the caller's fxc), one per response density (ground-state rows
     repeated)."""
@@ -1031,60 +774,17 @@ def _kernel_rows(mydf, rho0_dev, fxc, nrows, vwn=False):
     return out
 
 
-# ---- GGA ('b88,') response: (rho1, grad rho1) from the ladder, the fused kernel isdf_gga_b88_fxc, the GGA integration pass ----------
-def _density_passes_gga(mydf, dm_in, kpts):
-    """_density_passes with gradients: [(factor, spec4 (4, nset, gc))], the GGA integrator and nset."""
-    nao = mydf.cell.nao_nr()
-    dm_in = np.asarray(dm_in)
-    if kpts is None or mydf._is_gamma(kpts):
-        shape, dms = mydf._real_dms(dm_in)
-        return [(1.0, mydf._eval_rhoG_gga(dms))], (lambda sp4: mydf._integrate_gga(sp4).reshape(shape)), dms.shape[0]
-    kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-    dms = np.asarray(dm_in, dtype=np.complex128).reshape(-1, len(kpts), nao, nao)
-    passes = [(fac, mydf._eval_rhoG_gga_k(part, kpts)) for fac, part in mydf._hermitian_parts(dms)]
-    return passes, (lambda sp4: mydf._integrate_gga_k(sp4, kpts).reshape(dm_in.shape)), dms.shape[0]
-
-
-def _ground_density_gga(mydf, dm0, kpts, scale=1.0):
-    """scale * (rho, grad rho) of the ground-state matrix (or (alpha, beta) pair) on the dense mesh, device (4, nset, G)."""
-    passes, _, nset = _density_passes_gga(mydf, dm0, kpts)
-    spec4 = passes[0][1]
-    out = mydf.backend.empty((4, nset, int(np.prod(mydf.mesh))))
-    for c in range(4):
-        out[c].copy_(_real_space(mydf, spec4[c], scale / mydf.cell.vol))
-    return out
-
-
-def _response_gga(mydf, dms, kpts, contract, with_j, total_j=False, w_scale=1.0):
-    """veff[n] = GGA matrix of  w_scale * wv[n]  with wv = contract(rho1) (4, nset, G), rho1 = (rho, grad rho) of each response
-    matrix (+ Hartree potential of rho1[n], or of the pair's sum with total_j, on component 0)."""
-    be, cell = mydf.backend, mydf.cell
-    mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    G = int(np.prod(mesh))
-    weight = cell.vol / G
-    passes, integrate, nset = _density_passes_gga(mydf, dms, kpts)
-    veff = 0.0
-    for fac, spec4 in passes:
-        rho1 = be.empty((4, nset, G))
-        for c in range(4):
-            be.mg_restrict_potential(spec4[c], mesh, mesh, 1.0 / cell.vol, rho1[c])
-        wv = contract(rho1)
-        del rho1
-        if with_j:
-            be.mg_coulomb_kernel(spec4[0], mesh, cell.lattice_vectors())
-            if total_j:
-                _add_partner_hartree(mydf, spec4[0], nset)
-        else:
-            spec4[0].zero_()
-        spec4[1:].zero_()
-        for c in range(4):
-            be.mg_embed_density(wv[c], mesh, weight * w_scale, spec4[c], mesh, accumulate=True)
-        veff = veff + fac * integrate(spec4)
-    return np.asarray(veff)
+def _rows_contract(mydf, kernel_rows):
+    """One component (LDA): wv[0, n] = kernel_rows[n] * rho1[0, n], a row product in place."""
+    def contract(rho1):
+        for n in range(rho1.shape[1]):
+            mydf.backend.hadamard_rows(rho1[0, n:n + 1], kernel_rows[n:n + 1])
+        return rho1
+    return contract
 
 
 def _b88_contract(mydf, rho0):
-    """rho1 (4, nset, G) -> wv of the B88 kernel at rho0 (4, G) (device)."""
+    """rho1 (4, nset, G) -> wv of the B88 kernel at rho0 (4, G) (device; the fused kernel isdf_gga_b88_fxc)."""
     def contract(rho1):
         wv = mydf.backend.empty(tuple(rho1.shape))
         mydf.backend.gga_b88_fxc(rho0, rho1, wv)
@@ -1137,6 +837,14 @@ def _fxc_contract_spins(mydf, fxc):
     return contract
 
 
+def _closed_shell_contract(mydf, kind, r0, fxc, nset):
+    """The contract of a closed-shell kernel: the caller's ``fxc`` (nx, nx, G), else the functional's at the total density ``r0``
+    (ncomp, G) on the device.  LDA is the row product either way (``r0`` then only gives the row length under a caller's fxc)."""
+    if kind == 'b88':
+        return _fxc_contract(mydf, fxc) if fxc is not None else _b88_contract(mydf, r0)
+    return _rows_contract(mydf, _kernel_rows(mydf, r0, fxc, nset, vwn=kind == 'vwn'))
+
+
 def _b88_kernel_host(mydf, rho0):
     """(vxc (4, G), fxc (4, 4, G)) of B88 at rho0 (4, G) device: the potential of isdf_gga_b88 and the kernel's unique components
     written out by isdf_gga_b88_fxc."""
@@ -1155,16 +863,13 @@ def nr_rks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=No
     """Closed-shell response matrix f_xc[rho0] rho1 (+ J[rho1]) of the matrices ``dms`` (multigrid.py:1259-1318): 'lda,', 'lda,vwn'
     and 'b88,' (rho1 and grad rho1 from the ladder, the fused kernel on the dense mesh, the GGA integration pass)."""
     kind = _response_kind(xc_code)
-    be = mydf.backend
-    nset = _nset_of(mydf, dms, kpts)
-    if kind == 'b88':
-        if fxc is not None:
-            return _response_gga(mydf, dms, kpts, _fxc_contract(mydf, fxc), with_j)
-        r0 = be.to_device(np.asarray(rho0, dtype=np.float64).reshape(4, -1)) if rho0 is not None \
-            else _ground_density_gga(mydf, dm0, kpts)[:, 0]
-        return _response_gga(mydf, dms, kpts, _b88_contract(mydf, r0), with_j)
-    r0 = be.to_device(np.asarray(rho0, dtype=np.float64).reshape(1, -1)) if rho0 is not None else _ground_density(mydf, dm0, kpts)
-    return _response(mydf, dms, kpts, _kernel_rows(mydf, r0, fxc, nset, vwn=kind == 'vwn'), with_j)
+    ncomp = _ncomp(kind)
+    r0 = None
+    if ncomp == 1 or fxc is None:
+        r0 = mydf.backend.to_device(np.asarray(rho0, dtype=np.float64).reshape(ncomp, -1)) if rho0 is not None \
+            else _ground_density(mydf, dm0, kpts, ncomp=ncomp)[:, 0]
+    contract = _closed_shell_contract(mydf, kind, r0, fxc, _nset_of(mydf, dms, kpts))
+    return _response(mydf, dms, kpts, contract, with_j, ncomp=ncomp)
 
 
 def nr_rks_fxc_st(mydf, xc_code, dm0, dms_alpha, singlet=True, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
@@ -1172,28 +877,18 @@ def nr_rks_fxc_st(mydf, xc_code, dm0, dms_alpha, singlet=True, rho0=None, vxc=No
     For exchange alone f_ab = 0 and f_aa(rho0/2) = 2 f(rho0): singlet and triplet coincide.  A caller's fxc is the open-shell
     kernel (2, nx, 2, nx, G) of cache_xc_kernel1(spin=1).  'lda,vwn': the singlet only (f_aa + f_ab = 2 f(rho0))."""
     kind = _response_kind(xc_code, open_shell=not singlet)
+    ncomp = _ncomp(kind)
     be = mydf.backend
-    if kind == 'b88':
-        if fxc is not None:
-            f = np.asarray(fxc, dtype=np.float64)
-            f = f[0, :, 0] + f[0, :, 1] if singlet else f[0, :, 0] - f[0, :, 1]
-            return _response_gga(mydf, dms_alpha, kpts, _fxc_contract(mydf, f), False)
-        if rho0 is not None:
-            r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, 4, -1)[0])
-        else:
-            r0 = _ground_density_gga(mydf, dm0, kpts)[:, 0]
-        return _response_gga(mydf, dms_alpha, kpts, _b88_contract(mydf, r0), False, w_scale=2.0)
     if fxc is not None:
         f = np.asarray(fxc, dtype=np.float64)
         fxc = f[0, :, 0] + f[0, :, 1] if singlet else f[0, :, 0] - f[0, :, 1]
-        r0 = be.empty((1, fxc.size))
+        r0 = be.empty((1, fxc.size)) if ncomp == 1 else None
     elif rho0 is not None:
-        r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, -1)[:1])      # (rho_a, rho_b) in, total density out
+        r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, ncomp, -1)[0])   # (rho_a, rho_b) in, total density out
     else:
-        r0 = _ground_density(mydf, dm0, kpts)
-    nset = _nset_of(mydf, dms_alpha, kpts)
-    return _response(mydf, dms_alpha, kpts, _kernel_rows(mydf, r0, fxc, nset, vwn=kind == 'vwn'), False,
-                     w_scale=1.0 if fxc is not None else 2.0)
+        r0 = _ground_density(mydf, dm0, kpts, ncomp=ncomp)[:, 0]
+    contract = _closed_shell_contract(mydf, kind, r0, fxc, _nset_of(mydf, dms_alpha, kpts))
+    return _response(mydf, dms_alpha, kpts, contract, False, w_scale=1.0 if fxc is not None else 2.0, ncomp=ncomp)
 
 
 def nr_uks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=None, fxc=None, kpts=None, verbose=None):
@@ -1201,21 +896,17 @@ def nr_uks_fxc(mydf, xc_code, dm0, dms, hermi=0, with_j=False, rho0=None, vxc=No
     w_s = f_ss(rho0_s) rho1_s with f_ss(rho_s) = 2 f(2 rho_s) by spin scaling, the Coulomb term of with_j from rho1_a + rho1_b.
     A caller's fxc is the kernel (2, nx, 2, nx, G) of cache_xc_kernel1(spin=1), applied block by block."""
     kind = _response_kind(xc_code, open_shell=True)
-    be = mydf.backend
-    if kind == 'b88':
-        if fxc is not None:
-            return _response_gga(mydf, dms, kpts, _fxc_contract_spins(mydf, fxc), with_j, total_j=True)
-        if rho0 is not None:
-            r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, 4, -1).transpose(1, 0, 2))
-        else:
-            r0 = _ground_density_gga(mydf, dm0, kpts, scale=2.0)
-        return _response_gga(mydf, dms, kpts, _b88_contract_spins(mydf, r0), with_j, total_j=True, w_scale=2.0)
+    ncomp = _ncomp(kind)
     if fxc is not None:
-        return _response(mydf, dms, kpts, None, with_j, total_j=True, contract=_fxc_contract_spins(mydf, fxc))
-    r0 = be.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, -1)) if rho0 is not None \
-        else _ground_density(mydf, dm0, kpts, scale=2.0)
-    nset = _nset_of(mydf, dms, kpts)
-    return _response(mydf, dms, kpts, _kernel_rows(mydf, r0, None, nset), with_j, total_j=True, w_scale=2.0)
+        return _response(mydf, dms, kpts, _fxc_contract_spins(mydf, fxc), with_j, total_j=True, ncomp=ncomp)
+    if rho0 is not None:
+        r0 = mydf.backend.to_device(2.0 * np.asarray(rho0, dtype=np.float64).reshape(2, ncomp, -1).transpose(1, 0, 2))
+    else:
+        r0 = _ground_density(mydf, dm0, kpts, scale=2.0, ncomp=ncomp)
+    # r0 (ncomp, 2, G) = (2 rho_s, ...): what the spin-scaled kernel of each spin sees
+    contract = _b88_contract_spins(mydf, r0) if kind == 'b88' else \
+        _rows_contract(mydf, _kernel_rows(mydf, r0[0], None, _nset_of(mydf, dms, kpts)))
+    return _response(mydf, dms, kpts, contract, with_j, total_j=True, w_scale=2.0, ncomp=ncomp)
 
 
 def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
@@ -1225,11 +916,11 @@ def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
     fxc (2, 4, 2, 4, G) (spin scaling: the cross-spin blocks are zero)."""
     kind = _response_kind(xc_code, open_shell=spin == 1)
     be = mydf.backend
+    rho = _ground_density(mydf, dm, kpts, ncomp=_ncomp(kind))               # (ncomp, n_dm, G)
+    if spin == 0 and rho.shape[1] != 1:
+        raise ValueError('spin = 0 takes one density matrix')
     if kind == 'b88':
-        rho = _ground_density_gga(mydf, dm, kpts)                           # (4, n_dm, G)
         if spin == 0:
-            if rho.shape[1] != 1:
-                raise ValueError('spin = 0 takes one density matrix')
             r0 = rho[:, 0].contiguous()
             v, f = _b88_kernel_host(mydf, r0)
             return be.to_host(r0), v, f
@@ -1242,10 +933,8 @@ def cache_xc_kernel1(mydf, xc_code, dm, spin=0, kpts=None):
             v, f = _b88_kernel_host(mydf, be.to_device(np.ascontiguousarray(2.0 * r[sp])))
             vx[sp], fx[sp, :, sp] = v, 2.0 * f
         return np.ascontiguousarray(r), vx, fx
-    rho = _ground_density(mydf, dm, kpts)
+    rho = rho[0]
     if spin == 0:
-        if rho.shape[0] != 1:
-            raise ValueError('spin = 0 takes one density matrix')
         e, v, f = be.empty(tuple(rho.shape)), be.empty(tuple(rho.shape)), be.empty(tuple(rho.shape))
         be.lda_exchange(rho[0], e[0], v[0])
         be.lda_exchange_fxc(rho[0], f[0])
@@ -1305,60 +994,6 @@ def _gen_uhf_response(mf, dm0, with_j=True, hermi=0):
             return np.zeros_like(dm1)
         return nr_uks_fxc(mf.with_df, mf.xc, None, dm1, hermi, with_j, rho0, vxc, fxc, kpts)
     return vind
-
-
-def _nr_uks_gga(mydf, dm_in, with_j, return_j, kpts, kpts_band):
-    """Open-shell 'b88,': exchange functionals obey E_x[rho_a, rho_b] = (E_x[2 rho_a] + E_x[2 rho_b]) / 2, so each spin channel is
-    the closed-shell kernel at (2 rho_s, 2 grad rho_s) - potentials come out as they are, energies halved."""
-    be, cell = mydf.backend, mydf.cell
-    nao = cell.nao_nr()
-    if kpts is None:
-        shape, dms = mydf._real_dms(dm_in)
-        spec4 = mydf._eval_rhoG_gga(dms)
-        integrate_lda = lambda sp: mydf._integrate(sp).reshape(shape)            # noqa: E731
-        integrate_gga = lambda sp4: mydf._integrate_gga(sp4).reshape(shape)      # noqa: E731
-    else:
-        kpts = np.asarray(kpts, dtype=float).reshape(-1, 3)
-        dms = np.asarray(dm_in, dtype=np.complex128)
-        band_in = None if kpts_band is None else np.asarray(kpts_band, dtype=float)
-        band = kpts if band_in is None else band_in.reshape(-1, 3)
-        shape = dm_in.shape if band_in is None else ((2,) + ((len(band),) if band_in.ndim > 1 else ()) + (nao, nao))
-        spec4 = mydf._eval_rhoG_gga_k(0.5 * (dms + dms.conj().transpose(0, 1, 3, 2)), kpts)
-        integrate_lda = lambda sp: mydf._integrate_k(sp, band).reshape(shape)    # noqa: E731
-        integrate_gga = lambda sp4: mydf._integrate_gga_k(sp4, band).reshape(shape)   # noqa: E731
-    mesh = np.asarray(mydf.mesh, dtype=np.int32)
-    G = int(np.prod(mesh))
-    weight = cell.vol / G
-    rho2 = be.empty((4, 2, G))                                               # 2 rho_s and 2 grad rho_s
-    for c in range(4):
-        be.mg_restrict_potential(spec4[c], mesh, mesh, 2.0 / cell.vol, rho2[c])
-    vHspec = spec4[0].clone()
-    be.mg_coulomb_kernel(vHspec, mesh, cell.lattice_vectors())
-    vH = be.empty((2, G))
-    be.mg_restrict_potential(vHspec, mesh, mesh, 1.0 / cell.vol, vH)
-    exc, vrho, w = be.empty((2, G)), be.empty((2, G)), be.empty((3, 2, G))
-    nelec = excsum = ecoul = 0.0
-    for sp in range(2):
-        be.gga_b88(rho2[0, sp], rho2[1:, sp], exc[sp], vrho[sp], w[:, sp])
-        nelec += 0.5 * be.dot(rho2[0, sp]) * weight
-        excsum += 0.5 * be.dot(rho2[0, sp], exc[sp]) * weight
-        ecoul += 0.25 * (be.dot(rho2[0, sp], vH[0]) + be.dot(rho2[0, sp], vH[1])) * weight
-    vj = None
-    if return_j:
-        vj2 = integrate_lda(vHspec)
-        vj = vj2[0] + vj2[1]
-    spec4.zero_()
-    be.mg_embed_density(vrho, mesh, weight, spec4[0], mesh, accumulate=True)
-    for c in range(3):
-        be.mg_embed_density(w[c], mesh, weight, spec4[1 + c], mesh, accumulate=True)
-    if with_j:
-        vtot = be.empty((2, G))
-        for sp in range(2):
-            vtot[sp].copy_(vH[1 - sp])
-        be.mg_embed_density(vH, mesh, weight, spec4[0], mesh, accumulate=True)
-        be.mg_embed_density(vtot, mesh, weight, spec4[0], mesh, accumulate=True)
-    veff = integrate_gga(spec4)
-    return nelec, excsum, TaggedArray(veff, ecoul=ecoul, exc=excsum, vj=vj, vk=None)
 
 
 def multigrid_fftdf(mf):
