@@ -519,7 +519,19 @@ int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const double* d_
  *   isdf_gga_b88:               Becke-88 exchange ('b88,') of a spin-unpolarised density from rho and grad rho (three planes,
  *                               gstride apart): exc per particle, vrho = de/drho and w = de/d(grad rho) = 2 vsigma grad rho (three
  *                               planes, wstride apart); rho <= 1e-14 gives zero
- *   isdf_lda_exchange_fxc:      its second derivative f = d2(rho exc)/d rho2 (the LDA kernel of multigrid.py:1259-1452's response
+ *   isdf_xc_fused:              c_slater Slater + c_b88 B88 + c_vwn VWN + c_lyp LYP of a spin-unpolarised density in one pass (BLYP, the
+ *                               B3LYP family's semilocal part): inputs and outputs laid out as isdf_gga_b88's.  vwn_rpa = 0: fit V of
+ *                               the VWN paper (libxc LDA_C_VWN, as isdf_lda_vwn_add; B3LYP5), 1: its fit to the RPA energies (libxc
+ *                               LDA_C_VWN_RPA: A = 0.0310907, b = 13.0720, c = 42.7198, x0 = -0.409286; the reference's 'b3lyp').
+ *                               LYP (libxc GGA_C_LYP) in the form of Miehlich, Savin, Stoll and Preuss.  Slater / VWN vanish for
+ *                               rho <= 1e-24, B88 / LYP for rho <= 1e-14; a component with weight 0 is not evaluated
+ *   isdf_gga_lyp_polarised:     spin-polarised LYP times ``weight``: rho_s at d_rho + s sstride, component c of grad rho_s at d_grad +
+ *                               c gcstride + s sstride -> d_ec = weight e_c (energy density per VOLUME), d_vrho + s osstride (+)=
+ *                               weight de/d rho_s, d_w + c wcstride + s osstride (+)= weight de/d(grad rho_s) = weight (2 vsigma_ss
+ *                               grad rho_s + vsigma_ab grad rho_s'); accumulate = 1 adds to vrho and w (d_ec is always written).  A
+ *                               spin density <= 0 counts as zero with a zero gradient (e_c = 0, finite potentials); rho_a + rho_b
+ *                               <= 1e-14 gives zero
+ *   isdf_lda_exchange_fxc:      the second derivative of isdf_lda_exchange: f = d2(rho exc)/d rho2 (the LDA kernel of multigrid.py:1259-1452's response
  *                               functions; densities <= 1e-24 give zero)
  *   isdf_lda_vwn_fxc_add:       fxc += d2(rho eps_c)/d rho2 of the VWN5 correlation of isdf_lda_vwn_add (closed shell; densities
  *                               <= 1e-24 add nothing)
@@ -546,6 +558,11 @@ int isdf_lda_exchange(isdf_handle h, const double* d_rho, int64_t n, double* d_e
 int isdf_lda_vwn_add(isdf_handle h, const double* d_rho, int64_t n, double* d_exc, double* d_vxc);
 int isdf_gga_b88(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double* d_exc,
                  double* d_vrho, double* d_w, int64_t wstride);
+int isdf_xc_fused(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double c_slater, double c_b88,
+                  double c_vwn, int vwn_rpa, double c_lyp, double* d_exc, double* d_vrho, double* d_w, int64_t wstride);
+int isdf_gga_lyp_polarised(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gcstride, int64_t sstride, int64_t n,
+                           double weight, int accumulate, double* d_ec, double* d_vrho, double* d_w, int64_t wcstride,
+                           int64_t osstride);
 int isdf_lda_exchange_fxc(isdf_handle h, const double* d_rho, int64_t n, double* d_fxc);
 int isdf_lda_vwn_fxc_add(isdf_handle h, const double* d_rho, int64_t n, double* d_fxc);
 int isdf_gga_b88_fxc(isdf_handle h, const double* d_rho0, int64_t r0stride, int64_t n, const double* d_rho1, int64_t r1xstride,

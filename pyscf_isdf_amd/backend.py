@@ -569,6 +569,25 @@ class HipBackend:
         self.handle.call('isdf_gga_b88', self._p(rho), self._p(grad), grad.stride(0), rho.numel(), self._p(exc), self._p(vrho),
                          self._p(w), w.stride(0))
 
+    def xc_fused(self, rho, grad, coeffs, vwn_rpa, exc, vrho, w):
+        """rho (G,), grad (3, G) -> exc, vrho (G,), w (3, G) of coeffs = (c_slater, c_b88, c_vwn, c_lyp) in one pass; vwn_rpa
+        picks the RPA fit of VWN instead of fit V."""
+        self._stream()
+        assert rho.is_contiguous() and exc.is_contiguous() and vrho.is_contiguous() and grad.stride(1) == 1 and w.stride(1) == 1
+        cs, cb, cv, cl = (float(x) for x in coeffs)
+        self.handle.call('isdf_xc_fused', self._p(rho), self._p(grad), grad.stride(0), rho.numel(), cs, cb, cv, int(bool(vwn_rpa)), cl,
+                         self._p(exc), self._p(vrho), self._p(w), w.stride(0))
+
+    def gga_lyp_polarised(self, rho, weight, ec, vxc, accumulate=False):
+        """rho (4, 2, G) = (rho_s, grad rho_s) of the two spins -> ec (G,) = weight e_c (energy density) and
+        vxc (4, 2, G) (+)= weight (de/d rho_s, de/d grad rho_s); rho / vxc may be strided views (points contiguous)."""
+        self._stream()
+        G = rho.shape[2]
+        assert tuple(rho.shape) == (4, 2, G) and tuple(vxc.shape) == (4, 2, G) and rho.stride(2) == 1 and vxc.stride(2) == 1
+        assert ec.is_contiguous() and ec.numel() == G
+        self.handle.call('isdf_gga_lyp_polarised', self._p(rho), self._p(rho[1]), rho.stride(0), rho.stride(1), G, float(weight),
+                         int(bool(accumulate)), self._p(ec), self._p(vxc), self._p(vxc[1]), vxc.stride(0), vxc.stride(1))
+
     def lda_exchange_fxc(self, rho, fxc):
         self._stream()
         assert rho.is_contiguous() and fxc.is_contiguous() and rho.numel() == fxc.numel()

@@ -5,7 +5,8 @@
 //
 // What lives here: the spectrum traffic between a level mesh and the dense mesh (half spectra of real fields throughout:
 // D2Z / Z2D, (n0, n1, n2/2+1) complex per field), the rectangular density contraction rho = sum_(mu in A, nu in B) aoA D aoB,
-// the Coulomb kernel on a spectrum, the LDA exchange kernel and a deterministic dot product.  The rectangular potential
+// the Coulomb kernel on a spectrum, the functionals (Slater, VWN, Becke-88, LYP: one device function per point each, their own
+// kernels and the fused weighted sum), their second derivatives and a deterministic dot product.  The rectangular potential
 // integral V = aoA (v .* aoB)^T is isdf_gemm_nt with its per-k scale.
 //
 // Frequencies follow numpy.fft.fftfreq like the reference's index lists (multigrid.py:669-673): index i of an n-point axis
@@ -132,58 +133,80 @@ __global__ void rho_pair_reduce_kernel(const double* __restrict__ T, int64_t ldT
   rho[g] = s;
 }
 
+// Per-point functionals.  Each is written once and called from its own kernel and from the fused one (xc_fused_kernel).
+//
 // Slater exchange of a spin-unpolarised density: exc = -(3/4) (3/pi)^(1/3) rho^(1/3) per particle, vxc = (4/3) exc.
 // Densities at or below 1e-24 (the noise floor of the collocation, negative ripples of the FFT) give zero.
+__device__ inline void slater_point(double r, double& e, double& v) {
+  e = 0.0;
+  if (r > 1e-24) e = -0.75 * cbrt(3.0 / 3.14159265358979323846) * cbrt(r);
+  v = (4.0 / 3.0) * e;
+}
+
 __global__ void lda_exchange_kernel(const double* __restrict__ rho, int64_t n, double* __restrict__ exc, double* __restrict__ vxc) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double r = rho[i];
-  double e = 0.0;
-  if (r > 1e-24) e = -0.75 * cbrt(3.0 / 3.14159265358979323846) * cbrt(r);
+  double e, v;
+  slater_point(rho[i], e, v);
   exc[i] = e;
-  vxc[i] = (4.0 / 3.0) * e;
+  vxc[i] = v;
 }
 
-// VWN5 correlation of a spin-unpolarised density (libxc LDA_C_VWN, the correlation of the reference's 'lda,vwn'; Vosko, Wilk,
-// Nusair, Can. J. Phys. 58, 1200 (1980), eq. 4.4, paramagnetic parameters of fit V: A = 0.0310907, b = 3.72744, c = 12.9352,
-// x0 = -0.10498), ADDED to exc / vxc:  eps_c = A { ln(x^2/X) + 2b/Q atan(Q/(2x+b)) - b x0/X(x0) [ ln((x-x0)^2/X) +
-// 2(b+2 x0)/Q atan(Q/(2x+b)) ] },  x = sqrt(rs), X = x^2 + b x + c, Q = sqrt(4c - b^2);  v_c = eps_c - (x/6) d eps_c/dx.
-__global__ void lda_vwn_add_kernel(const double* __restrict__ rho, int64_t n, double* __restrict__ exc, double* __restrict__ vxc) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double r = rho[i];
+// VWN correlation of a spin-unpolarised density (Vosko, Wilk, Nusair, Can. J. Phys. 58, 1200 (1980), eq. 4.4) with the
+// paramagnetic parameters (A, b, c, x0) of one of the paper's fits:
+// eps_c = A { ln(x^2/X) + 2b/Q atan(Q/(2x+b)) - b x0/X(x0) [ ln((x-x0)^2/X) + 2(b+2 x0)/Q atan(Q/(2x+b)) ] },  x = sqrt(rs),
+// X = x^2 + b x + c, Q = sqrt(4c - b^2);  v_c = eps_c - (x/6) d eps_c/dx.  Densities at or below 1e-24 give zero.
+struct VwnFit { double A, b, c, x0; };
+// fit V (libxc LDA_C_VWN, the correlation of the reference's 'lda,vwn' and of B3LYP5) and the fit to the RPA energies (libxc
+// LDA_C_VWN_RPA, the correlation of the reference's 'b3lyp')
+__device__ inline VwnFit vwn_fit(int rpa) {
+  return rpa ? VwnFit{0.0310907, 13.0720, 42.7198, -0.409286} : VwnFit{0.0310907, 3.72744, 12.9352, -0.10498};
+}
+
+__device__ inline void vwn_point(double r, const VwnFit p, double& ec, double& vc) {
+  ec = 0.0;
+  vc = 0.0;
   if (!(r > 1e-24)) return;
-  const double A = 0.0310907, b = 3.72744, c = 12.9352, x0 = -0.10498;
+  const double A = p.A, b = p.b, c = p.c, x0 = p.x0;
   const double rs = cbrt(3.0 / (4.0 * 3.14159265358979323846 * r));
   const double x = sqrt(rs);
   const double X = x * x + b * x + c, X0 = x0 * x0 + b * x0 + c;
   const double Q = sqrt(4.0 * c - b * b);
   const double at = atan(Q / (2.0 * x + b));
-  const double ec = A * (log(x * x / X) + 2.0 * b / Q * at - b * x0 / X0 * (log((x - x0) * (x - x0) / X) + 2.0 * (b + 2.0 * x0) / Q * at));
+  ec = A * (log(x * x / X) + 2.0 * b / Q * at - b * x0 / X0 * (log((x - x0) * (x - x0) / X) + 2.0 * (b + 2.0 * x0) / Q * at));
   const double den = Q * Q + (2.0 * x + b) * (2.0 * x + b);
   const double dec = A * (2.0 / x - (2.0 * x + b) / X - 4.0 * b / den
                           - b * x0 / X0 * (2.0 / (x - x0) - (2.0 * x + b) / X - 4.0 * (b + 2.0 * x0) / den));
+  vc = ec - x / 6.0 * dec;
+}
+
+// VWN5 (fit V) ADDED to exc / vxc
+__global__ void lda_vwn_add_kernel(const double* __restrict__ rho, int64_t n, double* __restrict__ exc, double* __restrict__ vxc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = rho[i];
+  if (!(r > 1e-24)) return;
+  double ec, vc;
+  vwn_point(r, vwn_fit(0), ec, vc);
   exc[i] += ec;
-  vxc[i] += ec - x / 6.0 * dec;
+  vxc[i] += vc;
 }
 
 // Becke-88 exchange of a spin-unpolarised density (libxc GGA_X_B88; Becke, PRA 38, 3098): per spin channel
 // f(rho_s, g_s) = rho_s^(4/3) G(x), x = g_s / rho_s^(4/3), G = -C_x - beta x^2 / (1 + 6 beta x asinh x), C_x = (3/2)(3/4pi)^(1/3),
-// beta = 0.0042; e(rho, grad rho) = 2 f(rho/2, |grad rho|/2).  Outputs: exc = e / rho, vrho = de/drho, and the vector
-// w = de/d(grad rho) = 2 vsigma grad rho (what multiplies grad(phi_mu phi_nu) in the potential matrix).
-__global__ void gga_b88_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n,
-                               double* __restrict__ exc, double* __restrict__ vrho, double* __restrict__ w, int64_t wstride) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double r = rho[i];
-  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
-  double e = 0.0, vr = 0.0, wfac = 0.0;
+// beta = 0.0042; e(rho, grad rho) = 2 f(rho/2, |grad rho|/2).  Outputs: exc = e / rho, vrho = de/drho, and wfac with
+// w = de/d(grad rho) = 2 vsigma grad rho = wfac grad rho (what multiplies grad(phi_mu phi_nu) in the potential matrix).
+// rho <= 1e-14 gives zero.
+__device__ inline void b88_point(double r, double g2, double& e, double& vr, double& wfac) {
+  e = 0.0;
+  vr = 0.0;
+  wfac = 0.0;
   if (r > 1e-14) {
     const double beta = 0.0042;
     const double cx = 1.5 * cbrt(3.0 / (4.0 * 3.14159265358979323846));
     const double rs = 0.5 * r;
     const double r13 = cbrt(rs), r43 = rs * r13;
-    const double gs = 0.5 * sqrt(gx * gx + gy * gy + gz * gz);
+    const double gs = 0.5 * sqrt(g2);
     const double x = gs / r43;
     const double as = asinh(x);
     const double D = 1.0 + 6.0 * beta * x * as;
@@ -195,11 +218,154 @@ __global__ void gga_b88_kernel(const double* __restrict__ rho, const double* __r
     // de/d|grad rho| = 2 f_gs / 2 = G'(x);  w = G'(x) grad rho / |grad rho| = (G'/x) grad rho / (2 rho_s^(4/3))
     wfac = Gp_over_x / (2.0 * r43);
   }
+}
+
+__global__ void gga_b88_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n,
+                               double* __restrict__ exc, double* __restrict__ vrho, double* __restrict__ w, int64_t wstride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
+  double e, vr, wfac;
+  b88_point(rho[i], gx * gx + gy * gy + gz * gz, e, vr, wfac);
   exc[i] = e;
   vrho[i] = vr;
   w[i] = wfac * gx;
   w[wstride + i] = wfac * gy;
   w[2 * wstride + i] = wfac * gz;
+}
+
+// Lee-Yang-Parr correlation (libxc GGA_C_LYP; Lee, Yang, Parr, PRB 37, 785) in the gradient-only form of Miehlich, Savin, Stoll,
+// Preuss (CPL 157, 200), a = 0.04918, b = 0.132, c = 0.2533, d = 0.349.  With rho = rho_a + rho_b, t = rho^(-1/3),
+// omega = exp(-c t) t^11 / (1 + d t), delta = c t + d t / (1 + d t), K = 2^(11/3) (3/10) (3 pi^2)^(2/3), the energy density is
+//   e = -4a rho_a rho_b / (rho (1 + d t)) - a b omega G,
+//   G = K rho_a rho_b (rho_a^(8/3) + rho_b^(8/3)) + G_aa sigma_aa + G_ab sigma_ab + G_bb sigma_bb,
+//   G_aa = rho_a rho_b [(1 - 3 delta)/9 - (delta - 11)/9 rho_a/rho] - rho_b^2,  G_bb likewise,
+//   G_ab = rho_a rho_b (47 - 7 delta)/9 - (4/3) rho^2.
+// omega is formed from t (t^11 <= 1e52 at the threshold) and exp(-c t), which underflows to an exact zero below rho ~ 4e-11:
+// nothing overflows for rho down to 1e-14.  d omega/d rho = omega (delta - 11)/(3 rho), d delta/d rho = -t (c + d/(1+dt)^2)/(3 rho).
+// No division by a spin density: rho_b = 0 gives e = 0 and finite derivatives (LYP vanishes for a fully polarised density).
+// A spin density <= 0 counts as zero with a zero gradient; rho <= 1e-14 gives zero, as in b88_point.
+struct LypOut { double e, va, vb, vsaa, vsab, vsbb; };
+__device__ inline LypOut lyp_point(double ra, double rb, double saa, double sab, double sbb) {
+  LypOut o = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (!(ra > 0.0)) { ra = 0.0; saa = 0.0; sab = 0.0; }
+  if (!(rb > 0.0)) { rb = 0.0; sbb = 0.0; sab = 0.0; }
+  const double r = ra + rb;
+  if (!(r > 1e-14)) return o;
+  const double a = 0.04918, b = 0.132, c = 0.2533, d = 0.349;
+  const double pi = 3.14159265358979323846;
+  const double K = 8.0 * cbrt(4.0) * 0.3 * cbrt(9.0 * pi * pi * pi * pi);      // 2^(11/3) C_F, C_F = (3/10) (3 pi^2)^(2/3)
+  const double t = 1.0 / cbrt(r);
+  const double den = 1.0 + d * t;
+  const double t2 = t * t, t4 = t2 * t2, t8 = t4 * t4;
+  const double om = exp(-c * t) * (t8 * t2 * t) / den;
+  const double dl = c * t + d * t / den;
+  const double dlp = -t * (c + d / (den * den)) / (3.0 * r);
+  const double omp = om * (dl - 11.0) / (3.0 * r);
+  const double ca = cbrt(ra), cb = cbrt(rb);
+  const double ra83 = ra * ra * ca * ca, rb83 = rb * rb * cb * cb;             // rho_s^(8/3)
+  const double ab = ra * rb, xa = ra / r, xb = rb / r;
+  const double c1 = (1.0 - 3.0 * dl) / 9.0, c2 = (dl - 11.0) / 9.0, c3 = (47.0 - 7.0 * dl) / 9.0;
+  const double Gaa = ab * (c1 - c2 * xa) - rb * rb;
+  const double Gbb = ab * (c1 - c2 * xb) - ra * ra;
+  const double Gab = ab * c3 - (4.0 / 3.0) * r * r;
+  const double G = K * ab * (ra83 + rb83) + Gaa * saa + Gab * sab + Gbb * sbb;
+  // d/d rho_a and d/d rho_b of the three coefficients
+  const double Gaa_a = rb * (c1 - c2 * xa) + ab * (-dlp / 3.0 - dlp * xa / 9.0 - c2 * xb / r);
+  const double Gaa_b = ra * (c1 - c2 * xa) + ab * (-dlp / 3.0 - dlp * xa / 9.0 + c2 * xa / r) - 2.0 * rb;
+  const double Gbb_b = ra * (c1 - c2 * xb) + ab * (-dlp / 3.0 - dlp * xb / 9.0 - c2 * xa / r);
+  const double Gbb_a = rb * (c1 - c2 * xb) + ab * (-dlp / 3.0 - dlp * xb / 9.0 + c2 * xb / r) - 2.0 * ra;
+  const double Gab_a = c3 * rb - (7.0 / 9.0) * dlp * ab - (8.0 / 3.0) * r;
+  const double Gab_b = c3 * ra - (7.0 / 9.0) * dlp * ab - (8.0 / 3.0) * r;
+  const double G_a = K * rb * ((11.0 / 3.0) * ra83 + rb83) + Gaa_a * saa + Gab_a * sab + Gbb_a * sbb;
+  const double G_b = K * ra * ((11.0 / 3.0) * rb83 + ra83) + Gaa_b * saa + Gab_b * sab + Gbb_b * sbb;
+  // F1 = rho_a rho_b / (rho den):  dF1/d rho_a = rho_b/(rho den) [1 - x_a + x_a d t / (3 den)]
+  const double f1 = 1.0 / (r * den), f1t = d * t / (3.0 * den);
+  o.e = -4.0 * a * ab * f1 - a * b * om * G;
+  o.va = -4.0 * a * rb * f1 * (1.0 - xa + xa * f1t) - a * b * (omp * G + om * G_a);
+  o.vb = -4.0 * a * ra * f1 * (1.0 - xb + xb * f1t) - a * b * (omp * G + om * G_b);
+  o.vsaa = -a * b * om * Gaa;
+  o.vsab = -a * b * om * Gab;
+  o.vsbb = -a * b * om * Gbb;
+  return o;
+}
+
+// exc per particle, vrho and w of  cs Slater + cb B88 + cv VWN (fit V, or the RPA fit with vwn_rpa) + cl LYP  of a spin-unpolarised
+// density in one pass: 4 planes in, 5 planes out.  A component with weight 0 is not evaluated.  Closed-shell LYP is lyp_point at
+// rho_a = rho_b = rho/2, sigma_aa = sigma_ab = sigma_bb = sigma/4: vrho = va, w = (vsaa + vsab + vsbb)/2 grad rho.
+__global__ void xc_fused_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n, double cs,
+                                double cb, double cv, int vwn_rpa, double cl, double* __restrict__ exc, double* __restrict__ vrho,
+                                double* __restrict__ w, int64_t wstride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = rho[i];
+  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
+  const double g2 = gx * gx + gy * gy + gz * gz;
+  double e = 0.0, vr = 0.0, wfac = 0.0;
+  if (cs != 0.0) {
+    double es, vs;
+    slater_point(r, es, vs);
+    e += cs * es;
+    vr += cs * vs;
+  }
+  if (cb != 0.0) {
+    double eb, vb, wb;
+    b88_point(r, g2, eb, vb, wb);
+    e += cb * eb;
+    vr += cb * vb;
+    wfac += cb * wb;
+  }
+  if (cv != 0.0) {
+    double ec, vc;
+    vwn_point(r, vwn_fit(vwn_rpa), ec, vc);
+    e += cv * ec;
+    vr += cv * vc;
+  }
+  if (cl != 0.0 && r > 1e-14) {
+    const double s = 0.25 * g2;
+    const LypOut o = lyp_point(0.5 * r, 0.5 * r, s, s, s);
+    e += cl * o.e / r;
+    vr += cl * o.va;
+    wfac += cl * 0.5 * (o.vsaa + o.vsab + o.vsbb);
+  }
+  exc[i] = e;
+  vrho[i] = vr;
+  w[i] = wfac * gx;
+  w[wstride + i] = wfac * gy;
+  w[2 * wstride + i] = wfac * gz;
+}
+
+// Spin-polarised LYP, scaled by ``weight``: rho (spin s at s sstride), grad (component c of spin s at c gcstride + s sstride) ->
+// ec = weight e (energy DENSITY), vrho[s] (+)= weight de/d rho_s, w[s] (+)= weight de/d(grad rho_s) = weight (2 vs_ss grad rho_s +
+// vs_ab grad rho_s'), spin s at s osstride, component c of w at c wcstride.  LYP couples the spin channels: no spin scaling.
+__global__ void lyp_polarised_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gcstride, int64_t sstride,
+                                     int64_t n, double weight, int accumulate, double* __restrict__ ec, double* __restrict__ vrho,
+                                     double* __restrict__ w, int64_t wcstride, int64_t osstride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double ga[3], gb[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ga[c] = grad[c * gcstride + i];
+    gb[c] = grad[c * gcstride + sstride + i];
+  }
+  const double ra = rho[i], rb = rho[sstride + i];
+  // a spin density <= 0 counts as zero with a zero gradient (lyp_point does the same to the invariants)
+  if (!(ra > 0.0)) ga[0] = ga[1] = ga[2] = 0.0;
+  if (!(rb > 0.0)) gb[0] = gb[1] = gb[2] = 0.0;
+  const LypOut o = lyp_point(ra, rb, ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2],
+                             gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2]);
+  ec[i] = weight * o.e;
+  const double va = weight * o.va, vb = weight * o.vb;
+  if (accumulate) { vrho[i] += va; vrho[osstride + i] += vb; }
+  else { vrho[i] = va; vrho[osstride + i] = vb; }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double wa = weight * (2.0 * o.vsaa * ga[c] + o.vsab * gb[c]);
+    const double wb = weight * (2.0 * o.vsbb * gb[c] + o.vsab * ga[c]);
+    if (accumulate) { w[c * wcstride + i] += wa; w[c * wcstride + osstride + i] += wb; }
+    else { w[c * wcstride + i] = wa; w[c * wcstride + osstride + i] = wb; }
+  }
 }
 
 // second derivative of the Slater exchange energy density: f = d2(rho exc)/d rho2 = (4/9) C rho^(-2/3), C = -(3/4)(3/pi)^(1/3)
@@ -487,8 +653,33 @@ extern "C" int isdf_gga_b88(isdf_handle h, const double* d_rho, const double* d_
                             double* d_vrho, double* d_w, int64_t wstride) {
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_rho && d_grad && d_exc && d_vrho && d_w && n > 0 && gstride >= n && wstride >= n);
+  ProfScope ps(h, "gga_b88_kernel[byte]", 72.0 * (double)n);
   hipLaunchKernelGGL(gga_b88_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, d_grad, gstride, n, d_exc,
                      d_vrho, d_w, wstride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_xc_fused(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double c_slater,
+                             double c_b88, double c_vwn, int vwn_rpa, double c_lyp, double* d_exc, double* d_vrho, double* d_w,
+                             int64_t wstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_rho && d_grad && d_exc && d_vrho && d_w && n > 0 && gstride >= n && wstride >= n && (vwn_rpa == 0 || vwn_rpa == 1));
+  ProfScope ps(h, "xc_fused_kernel[byte]", 72.0 * (double)n);
+  hipLaunchKernelGGL(xc_fused_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, d_grad, gstride, n, c_slater, c_b88,
+                     c_vwn, vwn_rpa, c_lyp, d_exc, d_vrho, d_w, wstride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_gga_lyp_polarised(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gcstride, int64_t sstride,
+                                      int64_t n, double weight, int accumulate, double* d_ec, double* d_vrho, double* d_w,
+                                      int64_t wcstride, int64_t osstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_rho && d_grad && d_ec && d_vrho && d_w && n > 0 && gcstride >= n && sstride >= n && wcstride >= n && osstride >= n);
+  ProfScope ps(h, "lyp_polarised_kernel[byte]", 8.0 * (double)n * (17.0 + (accumulate ? 8.0 : 0.0)));
+  hipLaunchKernelGGL(lyp_polarised_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, d_grad, gcstride, sstride, n,
+                     weight, accumulate, d_ec, d_vrho, d_w, wcstride, osstride);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

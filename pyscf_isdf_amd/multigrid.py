@@ -25,13 +25,16 @@ What differs from the reference, by design for the GPU:
 Everything numerical runs in libmi355_isdf.so (multigrid.hip, eval_ao.hip, gemm_f64.hip); this file plans the levels and
 scatters the small level matrices into J on the host.
 
-Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc,
+Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, hybrid_coeff, nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc,
 cache_xc_kernel1, _gen_rhf_response, _gen_uhf_response, multi_grids_tasks, multigrid_fftdf - the names of
 pyscf/pbc/dft/multigrid/__init__.py and multigrid.py.
 
 K is the ISDF exchange of the parent class (``MultiGridFFTDF(ISDF)``): hybrid functionals get J/XC from here and K from the
 interpolation, which is the pairing SURVEY section 8 f-3 names.  XC: the Slater exchange ('lda,') and Becke's 1988 exchange
-('b88,', a GGA; Gamma point and k-points) in closed form - libxc is not part of this tree; both are pinned by the reference's SCF energies.  k-points: the same two passes on the periodic parts u_k, real and imaginary planes stacked so that the complex
+('b88,', a GGA; Gamma point and k-points) in closed form - libxc is not part of this tree; both are pinned by the reference's SCF energies.
+LYP correlation completes them to BLYP and to the semilocal part of the B3LYP family (_XC_TABLE; one fused launch per density,
+isdf_xc_fused; open shell: isdf_gga_lyp_polarised), pinned by the reference's BLYP constants; hybrid_coeff tells the caller how much
+of the ISDF K to add.  k-points: the same two passes on the periodic parts u_k, real and imaginary planes stacked so that the complex
 contractions are the Gamma point's real rectangular ones (get_j_kpts, nr_rks with kpts).
 """
 import copy
@@ -261,23 +264,48 @@ def _levels_of_runs(cell, ke_prim, tops, meshes, runs):
     return levels
 
 
-def _xc_kind(xc_code):
-    """'lda' (Slater exchange, with or without VWN5 correlation: _has_vwn), 'b88' (Becke-88 exchange, a GGA) or None."""
-    code = str(xc_code).replace(' ', '').upper()
-    if code in ('B88,', 'B88', 'GGA_X_B88,', 'GGA_X_B88'):
-        return 'b88'
-    return 'lda' if (_is_slater(xc_code) or _has_vwn(xc_code)) else None
+def _xc_rows():
+    """The functional table: normalised code (upper case, no blanks) -> (c_slater, c_b88, c_vwn, vwn_fit, c_lyp, hyb), the weights of
+    Slater exchange, Becke-88 exchange (which contains the Slater term), VWN correlation (fit 'V' = libxc LDA_C_VWN, or 'RPA' =
+    LDA_C_VWN_RPA), LYP correlation, and the fraction of exact exchange the caller adds."""
+    rows = {}
+    for codes, w in (
+            (('LDA,', 'SLATER,', 'LDA_X,', 'LDA', 'SLATER', 'LDA_X'), (1.0, 0.0, 0.0, 'V', 0.0, 0.0)),
+            (('LDA,VWN', 'LDA,VWN5', 'SLATER,VWN', 'SLATER,VWN5', 'SVWN', 'SVWN5', 'LDA_X,LDA_C_VWN', 'LDA,LDA_C_VWN'),
+             (1.0, 0.0, 1.0, 'V', 0.0, 0.0)),
+            (('B88,', 'B88', 'GGA_X_B88,', 'GGA_X_B88'), (0.0, 1.0, 0.0, 'V', 0.0, 0.0)),
+            (('BLYP', 'B88,LYP', 'GGA_X_B88,GGA_C_LYP'), (0.0, 1.0, 0.0, 'V', 1.0, 0.0)),
+            ((',LYP', ',GGA_C_LYP'), (0.0, 0.0, 0.0, 'V', 1.0, 0.0)),
+            # libxc.py:737-738 and the 2.3 note there: 'B3LYP' is the VWN-RPA variant (Gaussian's), 'B3LYP5' the fit-V one
+            (('B3LYP5', '.2*HF+.08*SLATER+.72*B88,.81*LYP+.19*VWN'), (0.08, 0.72, 0.19, 'V', 0.81, 0.2)),
+            (('B3LYP', 'B3LYPG'), (0.08, 0.72, 0.19, 'RPA', 0.81, 0.2))):
+        for c in codes:
+            rows[c] = w
+    return rows
 
 
-def _has_vwn(xc_code):
-    """'lda,vwn' (= Slater exchange + VWN5 correlation, libxc LDA_X + LDA_C_VWN; also spelled 'svwn', 'lda,vwn5')."""
-    code = str(xc_code).replace(' ', '').upper()
-    return code in ('LDA,VWN', 'LDA,VWN5', 'SLATER,VWN', 'SLATER,VWN5', 'SVWN', 'SVWN5', 'LDA_X,LDA_C_VWN', 'LDA,LDA_C_VWN')
+_XC_TABLE = _xc_rows()
 
 
-def _is_slater(xc_code):
-    code = str(xc_code).replace(' ', '').upper()
-    return code in ('LDA,', 'SLATER,', 'LDA_X,', 'LDA', 'SLATER', 'LDA_X')
+def _functional(xc_code):
+    """(c_slater, c_b88, c_vwn, vwn_fit, c_lyp, hyb) of ``xc_code``: a code of _XC_TABLE, or such a tuple itself (raw weights: always
+    the fused kernel).  Everything else raises NotImplementedError - libxc is not part of this tree."""
+    if isinstance(xc_code, (tuple, list)):
+        cs, cb, cv, fit, cl, hyb = xc_code
+        if fit not in ('V', 'RPA'):
+            raise ValueError("vwn_fit is 'V' or 'RPA'")
+        return float(cs), float(cb), float(cv), fit, float(cl), float(hyb)
+    w = _XC_TABLE.get(str(xc_code).replace(' ', '').upper())
+    if w is None:
+        raise NotImplementedError("xc=%r: 'lda,' (Slater exchange), 'lda,vwn' (+ VWN5 correlation), 'b88,' (Becke-88 exchange), 'blyp' / "
+                                  "'b88,lyp', ',lyp', 'b3lyp5' and 'b3lyp' / 'b3lypg' are implemented (no libxc in this tree)" % (xc_code,))
+    return w
+
+
+def hybrid_coeff(xc_code):
+    """Fraction of exact exchange of ``xc_code``: 0.2 for the B3LYP family, 0.0 for the other implemented functionals.  nr_rks
+    returns the semilocal part only, as the reference's does; the caller adds -hyb/2 K (closed shell) from ISDF.get_jk."""
+    return _functional(xc_code)[5]
 
 
 class _Planes:
@@ -577,7 +605,7 @@ def _real_space(mydf, spec, scale):
 
 
 def _ncomp(kind):
-    """Components the ladder carries for a functional: the density, or (a GGA) the density and its gradient."""
+    """Components the ladder carries for a response kind: the density, or (a GGA) the density and its gradient."""
     return 4 if kind == 'b88' else 1
 
 
@@ -589,43 +617,47 @@ def _kpts_or_gamma(mydf, kpts, kpts_band):
 
 
 def nr_rks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
-    """XC energy and potential matrix of a closed-shell density through the level ladder (multigrid.py:1046-1150): Slater
-    exchange (with or without VWN5 correlation) or Becke-88 exchange; Gamma point (real matrices) or k-points (dm (nk, nao, nao)
-    or (nset, nk, nao, nao), complex result on the k-points or on kpts_band).  Returns (nelec, exc, veff) with veff tagged
-    ecoul / exc / vj / vk like the reference's; with_j adds the Coulomb potential to veff before the integration pass (one pass
-    for J + XC)."""
-    if _xc_kind(xc_code) is None:
-        raise NotImplementedError("xc=%r: 'lda,' (Slater exchange), 'lda,vwn' (+ VWN5 correlation) and 'b88,' (Becke-88 exchange) are "
-                                  "implemented (no libxc in this tree)" % (xc_code,))
-    return _nr_ks(mydf, xc_code, dm_kpts, _kpts_or_gamma(mydf, kpts, kpts_band), kpts_band, with_j, return_j, False)
+    """XC energy and potential matrix of a closed-shell density through the level ladder (multigrid.py:1046-1150): the functionals
+    of _XC_TABLE - Slater exchange (with or without VWN5 correlation), Becke-88 exchange, BLYP, LYP alone and the semilocal part of
+    the B3LYP family (hybrid_coeff gives the exact-exchange fraction the caller adds); Gamma point (real matrices) or k-points
+    (dm (nk, nao, nao) or (nset, nk, nao, nao), complex result on the k-points or on kpts_band).  Returns (nelec, exc, veff) with
+    veff tagged ecoul / exc / vj / vk like the reference's; with_j adds the Coulomb potential to veff before the integration pass
+    (one pass for J + XC)."""
+    fn = _functional(xc_code)
+    return _nr_ks(mydf, fn, isinstance(xc_code, (tuple, list)), dm_kpts, _kpts_or_gamma(mydf, kpts, kpts_band), kpts_band, with_j,
+                  return_j, False)
 
 
 def nr_uks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
     """Open-shell form (multigrid.py:1152-1257): dm = (alpha, beta), each (nao, nao) at the Gamma point or (nk, nao, nao) at
     k-points.  Returns (nelec [both spins together], exc, veff (2, ...)); exchange functionals by spin scaling,
-    E_x[rho_a, rho_b] = (E_x[2 rho_a] + E_x[2 rho_b]) / 2, v_a = v_x[2 rho_a]; the Coulomb potential of with_j is that of the
-    total density."""
-    if _has_vwn(xc_code):
+    E_x[rho_a, rho_b] = (E_x[2 rho_a] + E_x[2 rho_b]) / 2, v_a = v_x[2 rho_a]; LYP ('blyp', ',lyp') from the spin-polarised kernel
+    on (rho_a, rho_b) together; the Coulomb potential of with_j is that of the total density.  Functionals with VWN correlation
+    ('lda,vwn', the B3LYP family) are refused: the spin-polarised VWN is not implemented."""
+    fn = _functional(xc_code)
+    if fn[2] != 0:
         raise NotImplementedError("xc=%r: the spin-polarised VWN correlation is not implemented (closed-shell nr_rks only)" % (xc_code,))
-    if _xc_kind(xc_code) is None:
-        raise NotImplementedError("xc=%r: 'lda,' (Slater exchange) and 'b88,' (Becke-88 exchange) are implemented (no libxc in this "
-                                  "tree)" % (xc_code,))
     kpts = _kpts_or_gamma(mydf, kpts, kpts_band)
     dm_in = np.asarray(dm_kpts)
     if dm_in.shape[0] != 2 or dm_in.ndim != (3 if kpts is None else 4):
         raise ValueError('nr_uks takes one pair (alpha, beta) of density matrices')
-    return _nr_ks(mydf, xc_code, dm_in, kpts, kpts_band, with_j, return_j, True)
+    return _nr_ks(mydf, fn, isinstance(xc_code, (tuple, list)), dm_in, kpts, kpts_band, with_j, return_j, True)
 
 
-def _nr_ks(mydf, xc_code, dm, kpts, kpts_band, with_j, return_j, spin):
+def _nr_ks(mydf, fn, raw, dm, kpts, kpts_band, with_j, return_j, spin):
     """The Kohn-Sham pass pair behind nr_rks and nr_uks: rho (and grad rho for a GGA, real-space gradients per level) from the
-    ladder, the functional on the dense mesh (isdf_lda_exchange [+ isdf_lda_vwn_add] or isdf_gga_b88), the potential
-    v_rho phi phi + (de/d grad rho) . grad(phi phi) back through the ladder.  ``kpts`` None: the Gamma point.  ``spin``: dm is
-    the pair (alpha, beta) and each spin channel is the closed-shell functional at (2 rho_s, 2 grad rho_s) - potentials come out
-    as they are, energies halved - with the Hartree potential of the total density."""
+    ladder, the functional ``fn`` (a row of _XC_TABLE) on the dense mesh, the potential v_rho phi phi + (de/d grad rho) .
+    grad(phi phi) back through the ladder.  The functional is one launch per density: isdf_lda_exchange [+ isdf_lda_vwn_add]
+    without gradients, isdf_gga_b88 for Becke's exchange alone, isdf_xc_fused for every other weighted sum (and for ``raw``
+    weights).  ``kpts`` None: the Gamma point.  ``spin``: dm is the pair (alpha, beta); each spin channel is the closed-shell
+    exchange at (2 rho_s, 2 grad rho_s) - potentials come out as they are, energies halved - LYP couples the channels and comes
+    from isdf_gga_lyp_polarised on (rho_a, rho_b), its energy added once; the Hartree potential is that of the total density."""
     be, cell = mydf.backend, mydf.cell
-    kind = _xc_kind(xc_code)
-    ncomp = _ncomp(kind)
+    cs, cb, cv, fit, cl, _ = fn
+    ncomp = 4 if (cb != 0 or cl != 0 or raw) else 1
+    pair_lyp = spin and cl != 0                                              # LYP of (rho_a, rho_b) together
+    if spin:
+        cv, cl = 0.0, 0.0                                                    # per channel: the exchange part alone
     dms, kpts, band, shape = mydf._format_dms(dm, kpts, kpts_band)
     # the XC functional sees the real density: the Hermitian part of D (the reference takes the real part of rho)
     spec = mydf._eval_rhoG(mydf._hermitian_parts(dms, anti=False)[0][1], kpts, ncomp)
@@ -638,23 +670,34 @@ def _nr_ks(mydf, xc_code, dm, kpts, kpts_band, with_j, return_j, spin):
     weight = cell.vol / G
     scale = 2.0 if spin else 1.0                                             # 2 rho_sigma: what the spin-scaled functional sees
     rho = _real_space(mydf, spec, scale / cell.vol)
+    rho_s = _real_space(mydf, spec, 1.0 / cell.vol) if pair_lyp else None     # the spin densities themselves, for LYP
     be.mg_coulomb_kernel(spec[0], mesh, cell.lattice_vectors())              # spec[0] now holds the Hartree potentials, set by set
     vH = _real_space(mydf, spec[:1], 1.0 / cell.vol)[0]
     exc = be.empty((nset, G))
     vxc = be.empty((ncomp, nset, G))                                         # v_rho and, for a GGA, de/d grad rho
     nelec, excsum, ecoul = np.zeros(nset), np.zeros(nset), np.zeros(nset)
+    per_channel = not (pair_lyp and cs == 0 and cb == 0)                     # ',lyp' of a pair: nothing but the coupled term
     for i in range(nset):
-        if kind == 'b88':
+        if not per_channel:
+            pass
+        elif ncomp == 1:
+            be.lda_exchange(rho[0, i], exc[i], vxc[0, i])
+            if cv != 0:
+                be.lda_vwn_add(rho[0, i], exc[i], vxc[0, i])
+        elif (cs, cb, cv, cl) == (0.0, 1.0, 0.0, 0.0) and not raw:
             be.gga_b88(rho[0, i], rho[1:, i], exc[i], vxc[0, i], vxc[1:, i])
         else:
-            be.lda_exchange(rho[0, i], exc[i], vxc[0, i])
-            if _has_vwn(xc_code):
-                be.lda_vwn_add(rho[0, i], exc[i], vxc[0, i])
+            be.xc_fused(rho[0, i], rho[1:, i], (cs, cb, cv, cl), fit == 'RPA', exc[i], vxc[0, i], vxc[1:, i])
         nelec[i] = be.dot(rho[0, i]) / scale * weight
-        excsum[i] = be.dot(rho[0, i], exc[i]) / scale * weight
+        if per_channel:
+            excsum[i] = be.dot(rho[0, i], exc[i]) / scale * weight
         # a spin's density meets the Hartree potential of both spins, a closed-shell density its own
         ecoul[i] = 0.5 / scale * sum(be.dot(rho[0, i], vH[j]) for j in (range(nset) if spin else (i,))) * weight
-    del exc, rho
+    e_pair = 0.0
+    if pair_lyp:
+        be.gga_lyp_polarised(rho_s, fn[4], exc[0], vxc, accumulate=per_channel)     # exc[0] is free again: the energy density
+        e_pair = be.dot(exc[0]) * weight
+    del exc, rho, rho_s
     vj = integrate(spec[:1]) if return_j else None
     # potential spectra: XC on every component; J stays where it is for a closed shell, and is added in real space for a pair
     spec[1:].zero_()
@@ -663,7 +706,7 @@ def _nr_ks(mydf, xc_code, dm, kpts, kpts_band, with_j, return_j, spin):
     for c in range(ncomp):
         be.mg_embed_density(vxc[c], mesh, weight, spec[c], mesh, accumulate=True)
     if spin:
-        nelec, excsum, ecoul = nelec.sum(), excsum.sum(), ecoul.sum()
+        nelec, excsum, ecoul = nelec.sum(), excsum.sum() + e_pair, ecoul.sum()
         if return_j:
             vj = vj[0] + vj[1]
         if with_j:                                                           # veff_sigma += the Hartree potential of the total density
@@ -734,11 +777,13 @@ def _add_partner_hartree(mydf, spec, nset):
 def _response_kind(xc_code, open_shell=False):
     """'lda' / 'vwn' / 'b88' for the response functions; open_shell: the spin-resolved kernel is needed (nr_uks_fxc, the triplet,
     cache_xc_kernel1(spin=1)) - for 'lda,vwn' that is the spin-polarised VWN, which is not implemented."""
-    kind = _xc_kind(xc_code)
-    if kind is None:
+    weights = None if isinstance(xc_code, (tuple, list)) else _XC_TABLE.get(str(xc_code).replace(' ', '').upper())
+    kind = {(1.0, 0.0, 0.0, 0.0): 'lda', (1.0, 0.0, 1.0, 0.0): 'vwn', (0.0, 1.0, 0.0, 0.0): 'b88'}.get(
+        None if weights is None else (weights[0], weights[1], weights[2], weights[4]))
+    if kind is None:                        # every code with LYP among them: its second derivatives are not built
         raise NotImplementedError("xc=%r: the response is implemented for 'lda,', 'lda,vwn' and 'b88,' (no libxc in this tree)"
                                   % (xc_code,))
-    if kind == 'lda' and _has_vwn(xc_code):
+    if kind == 'vwn':
         if open_shell:
             raise NotImplementedError("xc=%r: the spin-polarised VWN correlation is not implemented (open-shell and triplet "
                                       "response; the closed-shell nr_rks_fxc and the singlet are)" % (xc_code,))
