@@ -76,7 +76,8 @@ int isdf_release_workspace(isdf_handle h);
  * took a pivot), so that trailing updates and pivot steps skip pivoted columns; 0 keeps the whole matrix.  Same pivots either way.
  * The compaction stages 512 rows at a time in memory of its own (512 x m doubles at most, released before the call returns); if
  * that allocation fails, a line on stderr says so and the pick goes on over the whole matrix.  With profiling enabled, every
- * compaction adds to the "gram_compact[byte]" entry. */
+ * compaction adds to the "gram_compact[byte]" entry.
+ * "cand_gram": 1 (default) isdf_select_ip_ws uses its workspace for the blocks' Gram triangles; 0 = always the AO form. */
 int isdf_set_option(isdf_handle h, const char* key, int value);
 /* Range separation of the Gamma-point Coulomb kernel used by isdf_coulomb_W / _rows / _potential / isdf_get_j, as
  * pyscf/pbc/tools/pbc.py:408-418: omega > 0 long range (erf(omega r)/r), omega < 0 short range, 0 (default) plain 1/r.
@@ -172,6 +173,21 @@ int isdf_select_ip(isdf_handle h, const double* d_ao, int nao, int64_t ld,
                    int nblk, const int64_t* blk_off, const int32_t* nip,
                    double tol, double tie_rtol,
                    double* d_L, int64_t ldL, int64_t* d_piv, int32_t* rank);
+
+/* isdf_select_ip with a caller-supplied device workspace (d_work, work_bytes; may be NULL / 0).  With a workspace and option
+ * "cand_gram" = 1 the dot products of the pivot steps come from the blocks' Gram matrices S_b = ao_b^T ao_b, formed once on
+ * the matrix cores for as many consecutive blocks at a time as the workspace holds (isdf_select_ip_work_bytes per block);
+ * a pivot step then reads 8 m (j + 4) bytes where the plain form streams the AO slab again, 8 m (nao + j + 3).  Same
+ * rank, d_piv and d_L to the last bit.  Without a workspace, with the option off, or when one block alone does not fit,
+ * the call is isdf_select_ip.  With profiling enabled the Gram form shows as "cand_gram_transpose[byte]",
+ * "cand_gram_blocks[flop]" and "select_update_gram_kernel[byte]". */
+int isdf_select_ip_ws(isdf_handle h, const double* d_ao, int nao, int64_t ld,
+                      int nblk, const int64_t* blk_off, const int32_t* nip,
+                      double tol, double tie_rtol,
+                      double* d_L, int64_t ldL, int64_t* d_piv, int32_t* rank,
+                      void* d_work, int64_t work_bytes);
+/* Workspace bytes the Gram form needs for one block of m grid points with nao AO rows (blocks of a group add up). */
+int64_t isdf_select_ip_work_bytes(int nao, int64_t m);
 
 /* S2, refined stage: pivoted Cholesky of an EXPLICIT symmetric positive semidefinite matrix d_A (m x m, row-major,
  * leading dimension ldA, DESTROYED: it ends as scratch - the residual of the last stored order, which "gram_compact" may have

@@ -211,15 +211,22 @@ class HipBackend:
                          self._p(owner))
         return self.to_host(owner)
 
-    def select_ip(self, ao, blk_off, nip, tol, tie_rtol, L, piv):
-        """Returns rank (np.int32[nblk]); fills L (kmax, ldL) and piv (nblk, kmax) int64 (local indices)."""
+    def select_ip_work_bytes(self, nao, m):
+        """Workspace bytes one block of m grid points takes in select_ip's Gram form (blocks of a group add up)."""
+        return int(self.handle.lib.isdf_select_ip_work_bytes(int(nao), int(m)))
+
+    def select_ip(self, ao, blk_off, nip, tol, tie_rtol, L, piv, work=None):
+        """Returns rank (np.int32[nblk]); fills L (kmax, ldL) and piv (nblk, kmax) int64 (local indices).
+        work: optional contiguous device scratch for the blocks' Gram triangles (isdf_select_ip_ws): same result, fewer bytes."""
         self._stream()
         blk_off = np.ascontiguousarray(blk_off, dtype=np.int64)
         nip = np.ascontiguousarray(nip, dtype=np.int32)
         rank = np.zeros(len(nip), dtype=np.int32)
         assert piv.dtype == torch.int64 and piv.is_contiguous() and ao.stride(1) == 1 and L.stride(1) == 1
-        self.handle.call('isdf_select_ip', self._p(ao), ao.shape[0], ao.stride(0), len(nip), _np_ptr(blk_off),
-                         _np_ptr(nip), float(tol), float(tie_rtol), self._p(L), L.stride(0), self._p(piv), _np_ptr(rank))
+        assert work is None or work.is_contiguous()
+        self.handle.call('isdf_select_ip_ws', self._p(ao), ao.shape[0], ao.stride(0), len(nip), _np_ptr(blk_off),
+                         _np_ptr(nip), float(tol), float(tie_rtol), self._p(L), L.stride(0), self._p(piv), _np_ptr(rank),
+                         None if work is None else self._p(work), 0 if work is None else work.numel() * work.element_size())
         return rank
 
     def select_ip_gram(self, A, nip, tol, tie_rtol, piv, panel=0):

@@ -58,7 +58,10 @@ struct isdf_ctx {
   // pair-density rows aoP ao: 0 = rocBLAS dgemm (default: 74 TF/s on that shape), 1 = the own MFMA NN kernel of gemm_f64.hip with
   // the square fused into its epilogue (66-71 TF/s; kept as the library-free route and for A/B runs)
   int gemm_nn_own = 0;
-  int attr_gemm_b = 0, attr_gemm_nn = 0;   // dynamic-LDS attributes raised on this handle's device
+  int attr_gemm_b = 0, attr_gemm_nn = 0, attr_gram_tri = 0;   // dynamic-LDS attributes raised on this handle's device
+  // per-atom candidate selection: 1 = form the blocks' Gram triangles once on the matrix cores when the caller passes a
+  // workspace (default), 0 = always stream the AO slab at every pivot (select_ip.hip)
+  int cand_gram = 1;
   int conv_pipe = 1;         // plane passes of the convolution: 1 persistent workgroups with the next plane prefetched, 0 one workgroup per plane
   int conv_sub_rows = 0;     // rows per cache-resident sub-batch of the plane convolution (0: whole batch)
   int gram_pivot_tpb = 256;  // columns per workgroup of the Gram selection's pivot step (64, 128 or 256: measured 15.5 / 13.0 / 12.2 us per pivot)
@@ -180,3 +183,17 @@ int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A,
 int gemm_rm(isdf_handle h, char opA, char opB, int64_t M, int64_t N, int64_t K, double alpha,
             const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
             int64_t ldc);
+
+// ---- block-lower Gram triangles of the candidate selection (gemm_f64.hip, select_ip.hip) -------
+// Storage of the lower triangle of a symmetric m x m matrix in tile rows of 256: tile row tm holds its 256 rows with
+// (tm + 1) * 256 columns each, tile rows back to back.  Row r is valid in columns [0, min(m, ((r >> 8) + 1) * 256)).
+__host__ __device__ inline int64_t gram_tri_row(int64_t r) {        // offset of row r (doubles)
+  const int64_t tm = r >> 8;
+  return 32768 * tm * (tm + 1) + (r & 255) * ((tm + 1) << 8);
+}
+static inline int64_t gram_tri_size(int64_t m) { return m > 0 ? gram_tri_row(m - 1) + (((m - 1) >> 8) + 1) * 256 : 0; }
+struct GramTriUnit { int blk, tm, tn, pad; };   // 256 x 128 tile (tm, tn) of block blk, tn <= 2 tm + 1
+// S_b = X_b X_b^T for the units' blocks, one launch: X (points x K, K % 32 == 0, zero padded, row 0 = point row0),
+// d_blk_off absolute point offsets, d_tri_off the triangles' offsets in S; flop: the algorithmic work for the profile
+int gram_tri_blocks(isdf_handle h, const double* X, int64_t ldx, int K, const GramTriUnit* d_units, int64_t nunits,
+                    const int64_t* d_blk_off, int64_t row0, const int64_t* d_tri_off, double* S, double flop);

@@ -104,6 +104,7 @@ int isdf_set_option(isdf_handle h, const char* key, int value) {
     h->gram_pivot_tpb = value;
     return ISDF_OK;
   }
+  if (std::string(key) == "cand_gram") { h->cand_gram = value ? 1 : 0; return ISDF_OK; }
   if (std::string(key) == "gram_compact") { h->gram_compact = value ? 1 : 0; return ISDF_OK; }
   if (std::string(key) == "gram_compact_permille") {
     if (value < 1 || value > 1000) return isdf_fail(h, ISDF_ERR_ARG, "isdf_set_option: gram_compact_permille %d not in [1, 1000]", value);

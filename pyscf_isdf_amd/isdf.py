@@ -72,6 +72,8 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                                           # transform), amplified like it by cond(A')^2: above this c_isdf the probe check rejects it at configs[2]
         self.cand_skip_zero_rows = True   # the per-atom selections skip the AO rows that are identically zero on the atom's block of
                                           # grid points (the collocation truncates every shell at its rcut): same pivots, less traffic
+        self.cand_gram = True             # the per-atom selections read their dot products from the blocks' Gram triangles, formed once on
+                                          # the matrix cores in the unused part of the fit buffer (option "cand_gram"): same pivots to the bit
         self.cand_ao_cutoff = None        # 'refined', Bohr: the CANDIDATE stage of an atom's block sees only the AOs of atoms
                                           # within this distance (minimum image); None: all AOs.  The final pick always uses all.
         self.tie_rtol = 1e-10
@@ -413,7 +415,19 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         elif self.cand_skip_zero_rows:
             ao_sel = self._nonzero_ao_rows(ao_sel, scratch[nao + kmax:], blk_off)
         piv = be.empty((cell.natm, kmax), dtype=torch.int64)
-        rank = be.select_ip(ao_sel, blk_off, nip, self.select_tol, self.tie_rtol, L, piv)
+        kw = {}
+        if self.cand_gram and hasattr(be, 'select_ip_work_bytes'):      # (a backend without the Gram form takes no workspace)
+            # workspace of the Gram form: what the fit buffer has left behind phi, the Cholesky rows and the packed rows
+            used = nao + kmax + (0 if ao_sel.data_ptr() == scratch.data_ptr() else ao_sel.shape[0])
+            work = scratch[used:].reshape(-1)
+            need = [be.select_ip_work_bytes(ao_sel.shape[0], m) for m in counts]
+            if work.numel() * 8 < max(need) <= 1 << 30:
+                # a small cell's fit buffer cannot hold one block's triangle: a buffer of its own, at most 1 GiB
+                work = be.empty(((min(sum(need), 1 << 30) + 256) // 8,))
+            kw['work'] = work
+            del work
+        rank = be.select_ip(ao_sel, blk_off, nip, self.select_tol, self.tie_rtol, L, piv, **kw)
+        kw.clear()
         del ao_sel, L, scratch
         piv_h = be.to_host(piv)
         self._tick('S2_select_candidates' if self.select == 'refined' else 'S2_select_ip', t0)

@@ -37,6 +37,9 @@ SIGNATURES = {
     'isdf_gather_cols': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, c_i64]),
     'isdf_partition_by_atom': (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_dbl, c_vp]),
     'isdf_select_ip': (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp]),
+    'isdf_select_ip_ws': (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                  c_i64]),
+    'isdf_select_ip_work_bytes': (c_i64, [c_int, c_i64]),
     'isdf_select_ip_gram': (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_dbl, c_int, c_vp, ctypes.POINTER(ctypes.c_int32)]),
     'isdf_fit_from_chol': (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_vp]),
     'isdf_fit_prepare': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_dbl, c_vp, c_vp, ctypes.POINTER(c_dbl)]),
