@@ -587,6 +587,23 @@ int isdf_xc_fxc_apply(isdf_handle h, int nx, const double* d_fxc, int64_t fxstri
                       int64_t r1xstride, int64_t r1nstride, int nset, double* d_wv, int64_t wxstride, int64_t wnstride, int accumulate);
 int isdf_dot(isdf_handle h, const double* d_x, const double* d_y, int64_t n, double* result);
 
+/* The k-point M^q from ONE packed half spectrum of the real fit rows: by Parseval
+ *   M^q_PQ = (w/G) sum_G c_q(G) Y^_P(G) conj(Y^_Q(G)),  folded onto the half spectrum of the rows (they do not depend on q).
+ *   isdf_pack_table_pm:  from the full table d_tab (G) of one q (isdf_coulG_q) and the packed points d_idx (npts flat indices in
+ *                        n0 x n1 x (n2/2+1), as isdf_spectral_rows takes them):  d_s[2t] = d_s[2t+1] = scale (c(G_t) + (m_t - 1) c(-G_t)),
+ *                        d_a likewise with the minus sign; m_t = 1 on the kz = 0 and z-Nyquist planes, 2 between; -G is the
+ *                        index-wise negation (-i) mod n.  Both of length ldx (even, >= 2 npts), the padding zeroed.
+ *   isdf_herm_kscale_nt: Cre (M, ldc) = alpha sum_k A[m,k] s[k] B[n,k] + beta Cre,
+ *                        Cim (M, ldc) = alpha sum_k A[m,k] a[k] B~[n,k] + beta Cim,  B~[n,2j] = -B[n,2j+1], B~[n,2j+1] = B[n,2j],
+ *                        A (M, lda) and B (N, ldb) with K contiguous and the columns in consecutive (Re, Im) pairs
+ *                        (isdf_spectral_rows with unit scale).  ONE pass over the operands for both planes: hand-written
+ *                        v_mfma_f64_16x16x4_f64 kernel with two accumulator sets, i B formed at the LDS fragment read,
+ *                        deterministic slab reduction.  K % 16 == 0, even leading dimensions, 16-byte aligned operands and tables. */
+int isdf_pack_table_pm(isdf_handle h, const double* d_tab, const int32_t mesh[3], const int32_t* d_idx, int npts, double scale,
+                       double* d_s, double* d_a, int64_t ldx);
+int isdf_herm_kscale_nt(isdf_handle h, int M, int N, int64_t K, double alpha, const double* d_A, int64_t lda, const double* d_B,
+                        int64_t ldb, const double* d_s, const double* d_a, double beta, double* d_Cre, double* d_Cim, int64_t ldc);
+
 /* Dense helper behind S5/S6 (exposed for tests and micro-benchmarks):
  *   C (M, ldc) = alpha * A (M, lda) * (B (N, ldb) .* kscale[None, :])^T + beta * C,
  * K contiguous in both operands (the W = V Theta^T / vj = ao (v.ao)^T shape); d_kscale may be NULL.

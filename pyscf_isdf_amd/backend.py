@@ -513,6 +513,28 @@ class HipBackend:
         self.handle.call('isdf_gemm_nt', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(B), B.stride(0), ks,
                          float(beta), self._p(C), C.stride(0))
 
+    # ---- k-point M^q from the packed half spectra of the fit rows ------------------------------------
+    def pack_table_pm(self, table, mesh, idx, scale, s, a):
+        """s, a (ldx,) <- scale (c(G_t) +- (m_t - 1) c(-G_t)) on the packed points idx (int32 half-spectrum indices), each value on
+        both columns of its pair, padding zeroed (include/mi355_isdf.h isdf_pack_table_pm)."""
+        self._stream()
+        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+        assert idx.dtype == torch.int32 and table.is_contiguous() and table.numel() == int(np.prod(mesh))
+        assert s.is_contiguous() and a.is_contiguous() and s.numel() == a.numel()
+        self.handle.call('isdf_pack_table_pm', self._p(table), _np_ptr(mesh), self._p(idx), int(idx.numel()), float(scale),
+                         self._p(s), self._p(a), int(s.numel()))
+
+    def herm_kscale_nt(self, A, B, s, a, Cre, Cim, alpha=1.0, beta=0.0):
+        """Cre = alpha A diag(s) B^T + beta Cre, Cim = alpha A diag(a) (i B)^T + beta Cim for operands whose columns are
+        consecutive (Re, Im) pairs, in one pass (include/mi355_isdf.h isdf_herm_kscale_nt)."""
+        self._stream()
+        M, K = A.shape
+        N = B.shape[0]
+        assert B.shape[1] == K and tuple(Cre.shape) == (M, N) and tuple(Cim.shape) == (M, N) and Cre.stride() == Cim.stride()
+        assert A.stride(1) == 1 and B.stride(1) == 1 and Cre.stride(1) == 1 and s.numel() >= K and a.numel() >= K
+        self.handle.call('isdf_herm_kscale_nt', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(B), B.stride(0),
+                         self._p(s), self._p(a), float(beta), self._p(Cre), self._p(Cim), Cre.stride(0))
+
     # ---- multigrid ----------------------------------------------------------------------------
     def uniform_grid(self, mesh, a):
         """(3, G) device coordinates of the uniform grid, cell.get_uniform_grids' order and folding."""

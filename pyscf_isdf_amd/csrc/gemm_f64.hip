@@ -580,7 +580,220 @@ __global__ void reduce_slabs_kernel(const double* __restrict__ P, int nslab, int
   *q = (beta == 0.0) ? alpha * s : alpha * s + beta * (*q);
 }
 
+// ---- Hermitian twice-scaled NT product: the k-point M^q from the packed half spectra ------------------------
+//   Cre = alpha sum_k A[m,k] s[k] B[n,k] + beta Cre,   Cim = alpha sum_k A[m,k] a[k] B~[n,k] + beta Cim,
+//   B~[n,2j] = -B[n,2j+1], B~[n,2j+1] = B[n,2j]   (the columns are consecutive (Re, Im) pairs: B~ is i B).
+// One pass: every staged 128 x 16 A and B tile feeds BOTH accumulator sets.  128 x 128 tile, eight waves in a 2 x 4 grid, each
+// 64 rows x 32 columns = 4 x 2 accumulators per set (128 accumulator VGPRs for the two sets: the 256-register budget of two waves
+// per SIMD holds them without scratch).  A and B go to LDS as they are; a lane reads its B fragment element k AND its pair partner
+// k ^ 1 from LDS and multiplies them with s[k] and -+a[k] (the tables of the chunk sit in LDS next to the tiles; they are
+// pair-repeated, a[k] = a[k ^ 1]), so neither a scaled copy nor i B is ever stored.  Work units, XCD remap, double-buffered
+// 16-deep chunks and the fixed-order slab reduction are those of variant A above.  Aligned operands only: K % 16 == 0 (the packed
+// rows are zero padded to a multiple of 128 and so are the tables), 16-byte aligned rows and tables.
+constexpr int TPBH = 512;
+
+struct HermArgs {
+  const double* A; int64_t lda;
+  const double* B; int64_t ldb;
+  const double* s; const double* a;
+  double* Pre; double* Pim;      // partials [nslab][2][M][N] (or Cre / Cim themselves when direct)
+  int64_t ldp, slab_stride;
+  int M, N;
+  int64_t K, kslab;              // kslab multiple of BK
+  int ntm, ntn, nslab;
+  int64_t nunits, nunits_pad;
+  double alpha, beta;
+  int direct;
+};
+
+__global__ __launch_bounds__(TPBH, 2) void herm_kscale_nt_kernel(HermArgs g) {
+  extern __shared__ double smem[];                      // [2][BM*LDT] A | [2][BN*LDT] B | [2][2*BK] tables (s, then a)
+  double* sA = smem;
+  double* sB = smem + 2 * BM * LDT;
+  double* sT = smem + 2 * (BM + BN) * LDT;
+  const int64_t bid = blockIdx.x;
+  const int64_t per_xcd = g.nunits_pad / 8;
+  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  if (unit >= g.nunits) return;
+  const int tm = (int)(unit % g.ntm);
+  const int tn = (int)((unit / g.ntm) % g.ntn);
+  const int slab = (int)(unit / ((int64_t)g.ntm * g.ntn));
+  const int64_t k0 = (int64_t)slab * g.kslab;
+  const int64_t k1 = (k0 + g.kslab < g.K) ? k0 + g.kslab : g.K;
+  const int nchunks = (int)((k1 - k0) / BK);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;              // 2 x 4 waves, 64 rows x 32 columns each
+  const int srow = tid >> 3;                            // 0..63, +64
+  const int sseg = tid & 7;
+  const int mlast = g.M - 1, nlast = g.N - 1;
+  // rows past the matrix edge are clamped: computed, never stored
+  const double* pA0 = g.A + (int64_t)min(tm * BM + srow, mlast) * g.lda + k0 + sseg * 2;
+  const double* pA1 = g.A + (int64_t)min(tm * BM + srow + 64, mlast) * g.lda + k0 + sseg * 2;
+  const double* pB0 = g.B + (int64_t)min(tn * BN + srow, nlast) * g.ldb + k0 + sseg * 2;
+  const double* pB1 = g.B + (int64_t)min(tn * BN + srow + 64, nlast) * g.ldb + k0 + sseg * 2;
+  // the chunk's tables: threads 0..7 fetch s, threads 8..15 fetch a (one double2 each)
+  const bool tload = tid < 16;
+  const double* pT = (tid < 8 ? g.s : g.a) + k0 + sseg * 2;
+
+  double2 ra0, ra1, rb0, rb1, rt = make_double2(0.0, 0.0);
+#define ISDF_LOADH(C)                                                                         \
+  {                                                                                           \
+    const int off = (C) * BK;                                                                 \
+    ra0 = *reinterpret_cast<const double2*>(pA0 + off);                                       \
+    ra1 = *reinterpret_cast<const double2*>(pA1 + off);                                       \
+    rb0 = *reinterpret_cast<const double2*>(pB0 + off);                                       \
+    rb1 = *reinterpret_cast<const double2*>(pB1 + off);                                       \
+    if (tload) rt = *reinterpret_cast<const double2*>(pT + off);                              \
+  }
+#define ISDF_STH(P, R) { double* q_ = (P); q_[0] = R.x; q_[1] = R.y; }
+#define ISDF_STOREH(BUF)                                                                      \
+  {                                                                                           \
+    double* qa = sA + (BUF) * BM * LDT + srow * LDT + sseg * 2;                               \
+    double* qb = sB + (BUF) * BN * LDT + srow * LDT + sseg * 2;                               \
+    ISDF_STH(qa, ra0) ISDF_STH(qa + 64 * LDT, ra1) ISDF_STH(qb, rb0) ISDF_STH(qb + 64 * LDT, rb1) \
+    if (tload) ISDF_STH(sT + (BUF) * 2 * BK + (tid >> 3) * BK + sseg * 2, rt)                 \
+  }
+
+  d4 cre[4][2], cim[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { cre[i][j] = (d4){0.0, 0.0, 0.0, 0.0}; cim[i][j] = (d4){0.0, 0.0, 0.0, 0.0}; }
+
+  const int frow = lane & 15, fk = lane >> 4;
+  // global k of a fragment element is 16 c + 4 kk + fk (k0 is a multiple of 16): its parity is that of fk
+  const double sgn = (fk & 1) ? 1.0 : -1.0;
+  const int aoff = (wm * 64 + frow) * LDT, boff = (wn * 32 + frow) * LDT;
+  ISDF_LOADH(0)
+  ISDF_STOREH(0)
+  __syncthreads();
+  for (int c = 0; c < nchunks; ++c) {
+    const int buf = c & 1;
+    if (c + 1 < nchunks) ISDF_LOADH(c + 1)
+    const double* pa = sA + buf * BM * LDT + aoff;
+    const double* pb = sB + buf * BN * LDT + boff;
+    const double* pt = sT + buf * 2 * BK;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int k = kk * 4 + fk;
+      const double sv = pt[k], av = sgn * pt[BK + k];
+      double af[4], br[2], bi[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = pa[i * 16 * LDT + k];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        br[j] = sv * pb[j * 16 * LDT + k];
+        bi[j] = av * pb[j * 16 * LDT + (k ^ 1)];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          cre[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], br[j], cre[i][j], 0, 0, 0);
+          cim[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bi[j], cim[i][j], 0, 0, 0);
+        }
+    }
+    if (c + 1 < nchunks) ISDF_STOREH(buf ^ 1)
+    __syncthreads();
+  }
+
+  double* ore = g.Pre + (int64_t)slab * g.slab_stride;
+  double* oim = g.Pim + (int64_t)slab * g.slab_stride;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = tm * BM + wm * 64 + i * 16 + (lane >> 4) + 4 * r;
+      if (row >= g.M) continue;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = tn * BN + wn * 32 + j * 16 + (lane & 15);
+        if (col >= g.N) continue;
+        const int64_t o = (int64_t)row * g.ldp + col;
+        const double vr = cre[i][j][r], vi = cim[i][j][r];
+        if (g.direct) {
+          ore[o] = (g.beta == 0.0) ? g.alpha * vr : g.alpha * vr + g.beta * ore[o];
+          oim[o] = (g.beta == 0.0) ? g.alpha * vi : g.alpha * vi + g.beta * oim[o];
+        } else {
+          ore[o] = vr;
+          oim[o] = vi;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
+
+// Exposed as isdf_herm_kscale_nt (declared in include/mi355_isdf.h).
+extern "C" int isdf_herm_kscale_nt(isdf_handle h, int M, int N, int64_t K, double alpha, const double* d_A, int64_t lda,
+                                   const double* d_B, int64_t ldb, const double* d_s, const double* d_a, double beta,
+                                   double* d_Cre, double* d_Cim, int64_t ldc) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, M > 0 && N > 0 && K > 0 && d_A && d_B && d_s && d_a && d_Cre && d_Cim && lda >= K && ldb >= K && ldc >= N);
+  ARG_CHECK(h, K % BK == 0 && lda % 2 == 0 && ldb % 2 == 0 && ((uintptr_t)d_A) % 16 == 0 && ((uintptr_t)d_B) % 16 == 0 &&
+                   ((uintptr_t)d_s) % 16 == 0 && ((uintptr_t)d_a) % 16 == 0);
+  HermArgs g;
+  g.A = d_A; g.lda = lda; g.B = d_B; g.ldb = ldb; g.s = d_s; g.a = d_a;
+  g.M = M; g.N = N; g.K = K;
+  g.ntm = (int)cdiv(M, BM); g.ntn = (int)cdiv(N, BN);
+  const int64_t ntiles = (int64_t)g.ntm * g.ntn;
+  // one workgroup of eight waves per CU; slabs as in gemm_nt_f64_scaled: units to fill the device about 8 times over, at least
+  // 2048 deep, the two planes' partials at most 2 GiB, the slab count whose last round of units is fullest
+  const int64_t slots = (int64_t)h->num_cu;
+  int64_t nslab = cdiv(8 * slots, ntiles);
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(1, K / 2048),
+                                                             std::max<int64_t>(1, ((int64_t)2 << 30) / ((int64_t)M * N * 16))));
+  nslab = std::max<int64_t>(1, std::min<int64_t>(nslab, cap));
+  if (ntiles * nslab > slots) {
+    double best = 1e30;
+    int64_t pick = nslab;
+    for (int64_t c = nslab; c <= std::min<int64_t>(2 * nslab, cap); ++c) {
+      const double units = (double)ntiles * c;
+      const double waste = (double)(cdiv((int64_t)units, slots) * slots) / units;
+      if (waste < best - 1e-9) { best = waste; pick = c; }
+    }
+    nslab = pick;
+  }
+  g.kslab = cdiv(cdiv(K, nslab), BK) * BK;
+  g.nslab = (int)cdiv(K, g.kslab);
+  g.nunits = ntiles * g.nslab;
+  g.nunits_pad = cdiv(g.nunits, 8) * 8;
+  ARG_CHECK(h, g.nunits_pad < 2147483647LL);
+  g.alpha = alpha; g.beta = beta;
+  const int64_t plane = (int64_t)M * N;
+  if (g.nslab == 1) {
+    g.direct = 1; g.Pre = d_Cre; g.Pim = d_Cim; g.ldp = ldc; g.slab_stride = 0;
+  } else {
+    g.direct = 0;
+    g.Pre = (double*)isdf_ws(h, "gemm_partials", sizeof(double) * (size_t)g.nslab * 2 * plane);
+    if (!g.Pre) return ISDF_ERR_HIP;
+    g.Pim = g.Pre + plane;
+    g.ldp = N; g.slab_stride = 2 * plane;
+  }
+  const size_t lds = sizeof(double) * (2 * (BM + BN) * LDT + 4 * BK);
+  if (!h->attr_herm) {
+    HIP_TRY(h, hipFuncSetAttribute((const void*)herm_kscale_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    h->attr_herm = 1;
+  }
+  {
+    ProfScope ps(h, "herm_kscale_nt_kernel[flop]", 4.0 * M * N * (double)K);
+    hipLaunchKernelGGL(herm_kscale_nt_kernel, dim3((unsigned)g.nunits_pad), dim3(TPBH), lds, h->stream, g);
+    KERNEL_CHECK(h);
+  }
+  if (!g.direct) {
+    ProfScope ps(h, "gemm_reduce_slabs_kernel[byte]", 16.0 * (double)plane * (g.nslab + 1));
+    const unsigned nb = (unsigned)cdiv(plane, 256);
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(nb), dim3(256), 0, h->stream, g.Pre, g.nslab, g.slab_stride, M, N, alpha, beta,
+                       d_Cre, ldc);
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(nb), dim3(256), 0, h->stream, g.Pim, g.nslab, g.slab_stride, M, N, alpha, beta,
+                       d_Cim, ldc);
+    KERNEL_CHECK(h);
+  }
+  return ISDF_OK;
+}
 
 int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, const double* A, int64_t lda,
                        const double* B, int64_t ldb, const double* kscale, double beta, double* C,

@@ -312,6 +312,42 @@ extern "C" int isdf_nyquist_spectra(isdf_handle h, const double* d_rows, int nro
   return ISDF_OK;
 }
 
+// s[2t] = s[2t+1] = scale (c[G_t] + (m_t - 1) c[-G_t]),  a[2t] = a[2t+1] = scale (c[G_t] - (m_t - 1) c[-G_t]) for the half-spectrum
+// points idx[t] (flat index in n0 x n1 x (n2/2+1)); m_t = 1 on the kz = 0 and z-Nyquist planes, 2 between; -G is the index-wise
+// negation (-i) mod n of the full table.  Entries 2 npts .. ldx are zeroed.
+__global__ void pack_table_pm_kernel(const double* __restrict__ tab, const int32_t* __restrict__ idx, int npts, int n0, int n1, int n2,
+                                     double scale, double* __restrict__ s, double* __restrict__ a, int64_t ldx) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (2 * t >= ldx) return;
+  double ts = 0.0, ta = 0.0;
+  if (t < npts) {
+    const int n2h = n2 / 2 + 1;
+    const int hidx = idx[t];
+    const int kz = hidx % n2h, r = hidx / n2h;
+    const int j = r % n1, i = r / n1;
+    const int64_t pos = ((int64_t)i * n1 + j) * n2 + kz;
+    const int64_t neg = ((int64_t)((n0 - i) % n0) * n1 + (n1 - j) % n1) * n2 + (n2 - kz) % n2;
+    const double cp = tab[pos];
+    const double cm = (kz == 0 || 2 * kz == n2) ? 0.0 : tab[neg];
+    ts = scale * (cp + cm);
+    ta = scale * (cp - cm);
+  }
+  s[2 * t] = ts; s[2 * t + 1] = ts;
+  a[2 * t] = ta; a[2 * t + 1] = ta;
+}
+
+extern "C" int isdf_pack_table_pm(isdf_handle h, const double* d_tab, const int32_t mesh[3], const int32_t* d_idx, int npts,
+                                  double scale, double* d_s, double* d_a, int64_t ldx) {
+  // the two k-scale tables of isdf_herm_kscale_nt from the full kernel table of one q (isdf_coulG_q) on the packed points
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_tab && mesh && d_idx && d_s && d_a && npts > 0 && ldx % 2 == 0 && ldx >= 2 * (int64_t)npts);
+  ARG_CHECK(h, mesh[0] > 0 && mesh[1] > 0 && mesh[2] > 0 && (int64_t)mesh[0] * mesh[1] * (mesh[2] / 2 + 1) < 2147483647LL);
+  hipLaunchKernelGGL(pack_table_pm_kernel, dim3((unsigned)cdiv(ldx / 2, 256)), dim3(256), 0, h->stream, d_tab, d_idx, npts, mesh[0],
+                     mesh[1], mesh[2], scale, d_s, d_a, ldx);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
 extern "C" int isdf_zhadamard_planes(isdf_handle h, double* d_Ar, double* d_Ai, int64_t lda, const double* d_Br, const double* d_Bi,
                                      int64_t ldb, int rows, int64_t cols) {
   if (!h) return ISDF_ERR_ARG;

@@ -226,13 +226,37 @@ class FitRouteMixin:
         cg = be.coulG_half(mesh, a)                                  # (n0, n1, n2/2+1), 1/G inside
         if (cg < 0).any():
             return None
+        w = self.cell.vol / G
+
+        def share(pct, mult, box, keep):
+            # 'auto': the truncation is taken only when this mesh resolves the AO pair products - measured once per mesh on a few
+            # random products (phi^T c)(phi^T d): the share of their Coulomb energy that sits outside the sphere (coarse test
+            # meshes fail this by orders of magnitude; the production meshes of BASELINE.json read 1e-14 and less)
+            key = (tuple(int(x) for x in mesh), round(float(pct), 6))
+            if getattr(self, '_sphere_share', (None,))[0] != key:
+                self._sphere_share = (key, self._sphere_energy_share(mesh, cg, mult, box, keep, w))
+            return self._sphere_share[1]
+        pts = self._spectral_point_set(mesh, cg > 0, share)
+        if pts is None:
+            return None
+        idx, mult = pts
+        scale = np.sqrt(mult.ravel()[idx] * w * cg.ravel()[idx])
+        npts = len(idx)
+        ldx = -(-2 * npts // 128) * 128
+        return dict(idx=be.to_device(idx), scale=be.to_device(scale), npts=npts, ldx=ldx, fraction=2.0 * npts / G)
+
+    def _spectral_point_set(self, mesh, box, share):
+        """The packed points of a spectral W build, without any kernel scale (shared by the Gamma-point plan above and the k-point
+        build, kpoints._kspectral_prepare): (idx, mult) - the half-spectrum indices kept, in accumulation order, and the
+        multiplicities (n0, n1, n2/2+1) - or None when 'auto' refuses the sphere or nothing is left.  box: the half-spectrum points
+        that may be kept at all; share(pct, mult, box, keep): the guard's measure for w_sphere='auto', compared with w_sphere_tol."""
+        a = np.asarray(self.cell.lattice_vectors(), dtype=float)
         n0, n1, n2 = (int(x) for x in mesh)
         n2h = n2 // 2 + 1
-        keep = cg > 0
+        keep = box.copy()
         pct = getattr(self, 'w_sphere', 'auto')
         auto = isinstance(pct, str)
         pct = 100.0 if auto else float(pct or 0.0)
-        box = keep.copy()
         if pct > 0:
             b = 2 * np.pi * np.linalg.inv(a).T                       # rows b_i
             f0, f1, f2 = np.fft.fftfreq(n0, 1.0 / n0), np.fft.fftfreq(n1, 1.0 / n1), np.arange(n2h, dtype=float)
@@ -246,15 +270,8 @@ class FitRouteMixin:
         mult[:, :, 0] = 1.0
         if n2 % 2 == 0:
             mult[:, :, n2 // 2] = 1.0
-        w = self.cell.vol / G
         if auto:
-            # 'auto': the truncation is taken only when this mesh resolves the AO pair products - measured once per mesh on a few
-            # random products (phi^T c)(phi^T d): the share of their Coulomb energy that sits outside the sphere (coarse test
-            # meshes fail this by orders of magnitude; the production meshes of BASELINE.json read 1e-14 and less)
-            key = (tuple(int(x) for x in mesh), round(float(pct), 6))
-            if getattr(self, '_sphere_share', (None,))[0] != key:
-                self._sphere_share = (key, self._sphere_energy_share(mesh, cg, mult, box, keep, w))
-            if not (self._sphere_share[1] <= float(getattr(self, 'w_sphere_tol', 1e-11))):
+            if not (share(pct, mult, box, keep) <= float(getattr(self, 'w_sphere_tol', 1e-11))):
                 return None
         idx = np.flatnonzero(keep.ravel()).astype(np.int32)
         if len(idx) == 0:
@@ -272,10 +289,7 @@ class FitRouteMixin:
             g2p = np.einsum('xyzc,xyzc->xyz', Gv, Gv).ravel()[idx]
             bins = np.minimum((g2p * (nbins / g2p.max())).astype(np.int64), nbins - 1)
             idx = idx[np.argsort(-bins, kind='stable')]
-        scale = np.sqrt(mult.ravel()[idx] * w * cg.ravel()[idx])
-        npts = len(idx)
-        ldx = -(-2 * npts // 128) * 128
-        return dict(idx=be.to_device(idx), scale=be.to_device(scale), npts=npts, ldx=ldx, fraction=2.0 * npts / G)
+        return idx, mult
 
     def _sphere_energy_share(self, mesh, cg, mult, box, keep, w, ntest=8):
         """max over ntest random AO pair products t = (phi^T c)(phi^T d) of  E_outside / E_total,  E = (t | v | t) summed over the

@@ -85,6 +85,10 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                                           # exact on odd meshes only - on an even mesh the Nyquist index has no partner and the
                                           # wrap-around rule zeroes it for one sign of q (MgO 2x2x2 / 64^3: 7e-6 in K); False =
                                           # every q from its own kernel table; 'auto' = pair on all-odd meshes only
+        self.kpt_w_spectral = False       # k-points: True = every M^q from ONE packed half spectrum X of the (real, q-independent) fit rows:
+                                          # per q two table-scaled products over X in one pass (isdf_herm_kscale_nt), no FFT; the points
+                                          # kept follow w_sphere / w_sphere_tol / w_sort_bins as at the Gamma point (inside the sphere the
+                                          # +-q pairing is exact: no Nyquist-plane correction).  False: the classic convolution + products
         self.kpts_band = None             # band k-points of the last k-point build (set by get_jk(kpts_band=...))
         self.force_sharded = False       # run the multi-GPU code path even on one rank (tests)
         self.fit_route = 'auto'          # 'cholesky': forward solve over the grid (S3b), always safe;

@@ -278,6 +278,9 @@ class KPointMixin:
             self._kfit_state = dict(route=route, Y=Y, primary=primary, partner=partner, r_ip=r_ip, batch=batch, nao=nao, nh=nh, aoP_X=aoP_X,
                                     chol=None if route == 'blockjacobi' else chol,
                                     bj=(Afac, Dblk, ip_off) if route == 'blockjacobi' else None)
+            self._kfit_state['spec'] = self._kspectral_prepare(Y)
+            if self._kfit_state['spec'] is not None:
+                t0 = self._tick('S4_spectral_rows', t0)
             self._Wq, check, t0 = self._build_Wq(None, t0, probe=(route == 'blockjacobi' and self.fit_route == 'auto'))
             self.fit_route_used = route
             if route == 'blockjacobi' and self.fit_route == 'auto':
@@ -403,6 +406,7 @@ class KPointMixin:
         P, G = Y.shape
         mesh = np.asarray(self.mesh, dtype=np.int32)
         w = cell.vol / G
+        spec = st.get('spec')
         Wre = self._buffer('Wre', (P, P))
         Wim = self._buffer('Wim', (P, P))
         out, check = {}, 0.0
@@ -411,11 +415,20 @@ class KPointMixin:
                 continue
             q = self._qs[iq]
             coulG = be.coulG_q(mesh, cell.lattice_vectors(), q, omega=omega)
-            be.coulomb_Wq(Y, mesh, coulG, w, 0, P, st['batch'], Wre, Wim, upper_only=True)
-            be.symmetrize_hermitian(Wre, Wim)
+            if spec is not None:
+                self._kspectral_Mq(spec, coulG, Wre, Wim)
+            else:
+                be.coulomb_Wq(Y, mesh, coulG, w, 0, P, st['batch'], Wre, Wim, upper_only=True)
+                be.symmetrize_hermitian(Wre, Wim)
             jq = int(st['partner'][iq])
             twin = None
-            if self._pair_correct and jq >= 0 and jq != iq:
+            if spec is not None:
+                # no packed point on a Nyquist plane (any sphere): coulG_{-q}(G) = coulG_q(-G) on every point, the twin is the plain
+                # conjugate (taken where it is used, _jk_from_Wq).  The whole box of an even mesh: the twin from its OWN tables
+                if self._pair_correct and jq >= 0 and jq != iq and not spec['pair_exact']:
+                    twin = (be.empty((P, P)), be.empty((P, P)))
+                    self._kspectral_Mq(spec, be.coulG_q(mesh, cell.lattice_vectors(), -np.asarray(q), omega=omega), twin[0], twin[1])
+            elif self._pair_correct and jq >= 0 and jq != iq:
                 # M^{-q} = conj(M^q) + the Nyquist-plane terms the pairing misses on an even mesh; finished like M^q below
                 twin = (be.empty((P, P)), be.empty((P, P)))
                 twin[0].copy_(Wre)
@@ -453,6 +466,75 @@ class KPointMixin:
                 out[jq] = self._keep_Wq(Wt)
                 del twin, Wt
         return out, check, t0
+
+    # ---- kpt_w_spectral: every M^q from one packed half spectrum of the fit rows --------------------------------------------------
+    def _kspectral_prepare(self, Y):
+        """X (P, ldx) = the half spectra of the real fit rows Y on the packed points (fit_route._spectral_point_set: sphere,
+        multiplicities, shell order; unit scale, consecutive (Re, Im) pairs, zero padded), made ONCE per fit: the rows do not depend
+        on q, so every M^q - of this build and of later kernels on the kept fit - is two table-scaled products over X
+        (_kspectral_Mq), without any transform.  None (the classic build) when kpt_w_spectral is off, the plane FFT does not cover
+        the mesh, or w_sphere='auto' refuses the sphere.  Records the form in w_spectral_fraction."""
+        self.w_spectral_fraction = None
+        if self.kpt_w_spectral is False:
+            return None
+        if self.kpt_w_spectral is not True:
+            raise ValueError('kpt_w_spectral must be True or False')
+        be = self.backend
+        mesh = np.asarray(self.mesh, dtype=np.int32)
+        nbat = int(self.fft_batch or 512)
+        if not be.spectral_supported(mesh, nbat):
+            return None
+        n0, n1, n2 = (int(x) for x in mesh)
+        pts = self._spectral_point_set(mesh, np.ones((n0, n1, n2 // 2 + 1), dtype=bool), self._ksphere_share)
+        if pts is None:
+            return None
+        idx = pts[0]
+        P, G = Y.shape
+        npts = len(idx)
+        ldx = -(-2 * npts // 128) * 128
+        # the +-q pairing is exact when no packed point lies on the Nyquist plane of an even axis (DESIGN.md section 6b)
+        i2 = idx % (n2 // 2 + 1)
+        i1 = (idx // (n2 // 2 + 1)) % n1
+        i0 = idx // ((n2 // 2 + 1) * n1)
+        on_nyq = np.zeros(npts, dtype=bool)
+        for i, n in ((i0, n0), (i1, n1), (i2, n2)):
+            if n % 2 == 0:
+                on_nyq |= (i == n // 2)
+        d_idx = be.to_device(idx)
+        X = self._buffer('kspecX', (P, ldx))
+        be.spectral_rows(Y, mesh, d_idx, be.to_device(np.ones(npts)), X, batch=nbat)
+        self.w_spectral_fraction = 2.0 * npts / G
+        return dict(X=X, idx=d_idx, npts=npts, ldx=ldx, pair_exact=not on_nyq.any(), strip=nbat,
+                    s=self._buffer('kspec_s', (ldx,)), a=self._buffer('kspec_a', (ldx,)))
+
+    def _ksphere_share(self, pct, mult, box, keep):
+        """The guard of w_sphere='auto' at k-points: fit_route._sphere_energy_share on the rows of self.ao, here the stacked
+        periodic-part planes (Re and Im of every u^k), with the plain q = 0 kernel table.  Measured once per mesh.  A table with
+        negative entries (a truncated or attenuated kernel left active in the backend) gives no energy share: the guard refuses."""
+        mesh = np.asarray(self.mesh, dtype=np.int32)
+        key = ('kpts', tuple(int(x) for x in mesh), round(float(pct), 6))
+        if getattr(self, '_sphere_share', (None,))[0] != key:
+            cg = self.backend.coulG_half(mesh, np.asarray(self.cell.lattice_vectors(), dtype=float))
+            share = np.inf if (cg < 0).any() else \
+                self._sphere_energy_share(mesh, cg, mult, box, keep, self.cell.vol / int(np.prod(mesh)))
+            self._sphere_share = (key, share)
+        return self._sphere_share[1]
+
+    def _kspectral_Mq(self, spec, coulG, Mre, Mim):
+        """Mre + i Mim <- M^q = (w / G) sum_G c_q(G) Y^_P(G) conj(Y^_Q(G)) over the packed points, folded onto the half spectrum:
+            Re M = sum_j ts_j (Re Re + Im Im)_j,  Im M = sum_j ta_j (Im Re - Re Im)_j,  ts/ta_j = (w / G) [c_q(G_j) +- (m_j - 1) c_q(-G_j)],
+        one pass per strip of rows over X for both planes (isdf_herm_kscale_nt), block-upper part, mirrored at the end."""
+        be = self.backend
+        X = spec['X']
+        P = X.shape[0]
+        mesh = np.asarray(self.mesh, dtype=np.int32)
+        G = int(np.prod(mesh))
+        be.pack_table_pm(coulG, mesh, spec['idx'], self.cell.vol / G / G, spec['s'], spec['a'])
+        nb = spec['strip']
+        for b0 in range(0, P, nb):
+            b1 = min(P, b0 + nb)
+            be.herm_kscale_nt(X[b0:b1], X[b0:], spec['s'], spec['a'], Mre[b0:b1, b0:], Mim[b0:b1, b0:])
+        be.symmetrize_hermitian(Mre, Mim)
 
     def _nyquist_planes(self):
         """For every even mesh axis: the DFT of the fit rows on that axis' Nyquist plane (P x plane entries, real and imaginary
