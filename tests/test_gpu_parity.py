@@ -466,7 +466,8 @@ def test_isdf_object_vs_oracle_pipeline_diamond():
                                           (512, 300, 8192, False), (1000, 130, 65536, True), (256, 128, 32, False)])
 def test_gemm_nt_mfma(be, M, N, K, scaled):
     """The FP64 MFMA kernel behind W and vj: C = alpha A (B.*s)^T + beta C against numpy, incl. ragged
-    tiles, odd K / unaligned rows (generic path) and multi-slab reduction.  1e-12 relative to |A||B|."""
+    tiles, odd K / unaligned rows (generic path) and multi-slab reduction.  1e-12 relative to |A||B|.  The sweep over every
+    kernel instantiation, edge, stride and scalar pair, with an exact integer reference, is tests/test_gpu_gemm_sweep.py."""
     rng = np.random.default_rng(M * 7 + N)
     A = rng.standard_normal((M, K)); B = rng.standard_normal((N, K)); C0 = rng.standard_normal((M, N))
     s = rng.standard_normal(K) if scaled else None
