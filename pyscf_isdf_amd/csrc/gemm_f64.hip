@@ -23,6 +23,11 @@
 //        64 -> 69 TF/s, and it keeps co-scheduled workgroups in step so that shared operand panels hit in L2 (fabric
 //        traffic 3.9x -> 1.3x the algorithmic bytes).
 //    Algorithmic work: 2*M*N*K flop; bound: FP64 MFMA (78.6 TF/s).
+//  * Every kernel finds its unit with xcd_unit / decode_tile / slab_range (the NN form: decode_supertile) and stores its
+//    accumulators with ISDF_STORE_ACC.  Variant B's unit body, tile_256x128, is a function template that leaves the tile in
+//    accumulator registers: gemm_nt_mfma_kernel_b and the Gram triangles are that body between two ways of finding a unit
+//    and of storing it, and a new user writes a kernel that decodes its unit, calls it and stores.  The NN form keeps a main
+//    loop of its own: as a B-operand policy of tile_256x128 it compiled to another loop than the one measured.
 #include "common.h"
 #include <cstdlib>
 
@@ -63,6 +68,67 @@ struct GemmArgs {
   int direct;
 };
 
+// ---- what the kernels share: unit decode, accumulator store, issue order ------------------------------------------------------------
+// XCD-aware unit id: hardware deals consecutive block ids round-robin over 8 XCDs; give each XCD a
+// contiguous range of units so that neighbours (which share operand panels) share an L2.  Units past the caller's count are
+// the padding of the last round.
+__device__ __forceinline__ int64_t xcd_unit(int64_t nunits_pad) {
+  const int64_t bid = blockIdx.x;
+  const int64_t per_xcd = nunits_pad / 8;
+  return (bid % 8) * per_xcd + bid / 8;
+}
+
+struct Tile { int tm, tn, slab; };      // slab stays 0 where K is not cut (NN)
+struct KRange { int64_t k0, k1; };
+
+// slab-major units, row tile fastest
+__device__ __forceinline__ Tile decode_tile(int64_t unit, int ntm, int ntn) {
+  return {(int)(unit % ntm), (int)((unit / ntm) % ntn), (int)(unit / ((int64_t)ntm * ntn))};
+}
+
+__device__ __forceinline__ KRange slab_range(int slab, int64_t kslab, int64_t K) {
+  const int64_t k0 = (int64_t)slab * kslab;
+  return {k0, (k0 + kslab < K) ? k0 + kslab : K};
+}
+
+// epilogue: D[row = (lane>>4) + 4r][col = lane&15] per 16x16 accumulator; (ROW0, COL0) is the corner of the wave's NI x NJ
+// accumulators, entries past the M x N edge are dropped.  STORE is a statement that sees i, j, r, row and col.  A macro, not a
+// function template: through a functor the stores of the NT kernels compiled to another epilogue than the one measured.
+#define ISDF_STORE_ACC(NI, NJ, ROW0, COL0, M, N, STORE)                                       \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                            \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                           \
+      const int row = ROW0 + i * 16 + (lane >> 4) + 4 * r;                                    \
+      if (row >= M) continue;                                                                 \
+      _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                        \
+        const int col = COL0 + j * 16 + (lane & 15);                                          \
+        if (col >= N) continue;                                                               \
+        STORE                                                                                 \
+      }                                                                                       \
+    }                                                                                         \
+  }
+// STORE of the NT kernels: the slab's partial tile, or C itself (direct) with alpha and beta
+#define ISDF_SLAB_STORE                                                                       \
+  {                                                                                           \
+    double* q = out + (int64_t)row * g.ldp + col;                                             \
+    const double v = acc[i][j][r];                                                            \
+    if (g.direct) *q = (g.beta == 0.0) ? g.alpha * v : g.alpha * v + g.beta * (*q);           \
+    else *q = v;                                                                              \
+  }
+
+// 16 MFMAs of one k-step of a 4 x 4 accumulator block
+#define ISDF_MFMA16(AF, BF)                                                                   \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                             \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                           \
+        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[i], BF[j], acc[i][j], 0, 0, 0);
+// issue order inside a k-step region (variants B and D, NN): one LDS fragment read (of the NEXT k-step) after every second MFMA,
+// so that the reads trickle in under the MFMAs instead of in one burst (+1%); the first NX of the eight rounds carry one more
+// instruction of class XMASK (0x020: a global load of the chunk after next, 0x200: an LDS write of the next chunk), which
+// leaves only the barrier at the end of the chunk.  (0, 0) = no extra instruction: the mask of a round that never comes is
+// not read (the dead branch folds away once the loop is unrolled)
+#define ISDF_ISSUE(XMASK, NX) _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {              \
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
+    if (q_ < (NX)) __builtin_amdgcn_sched_group_barrier(XMASK, 1, 0); }
+
 // FAST: lda, ldb even (16-byte aligned rows given 16-byte aligned bases) and no K tail handling
 // needed inside a chunk (K % BK == 0).  Otherwise the generic path loads element-wise with guards.
 template <bool FAST>
@@ -70,17 +136,11 @@ __global__ __launch_bounds__(TPB, 2) void gemm_nt_mfma_kernel(GemmArgs g) {
   __shared__ double sA[2][BM * LDT];
   __shared__ double sB[2][BN * LDT];
 
-  // XCD-aware unit id: hardware deals consecutive block ids round-robin over 8 XCDs; give each XCD a
-  // contiguous range of units so that neighbours (which share operand panels) share an L2.
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = g.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int64_t unit = xcd_unit(g.nunits_pad);
   if (unit >= g.nunits) return;
-  const int tm = (int)(unit % g.ntm);
-  const int tn = (int)((unit / g.ntm) % g.ntn);
-  const int slab = (int)(unit / ((int64_t)g.ntm * g.ntn));
-  const int64_t k0 = (int64_t)slab * g.kslab;
-  const int64_t k1 = (k0 + g.kslab < g.K) ? k0 + g.kslab : g.K;
+  const Tile t = decode_tile(unit, g.ntm, g.ntn);
+  const KRange kr = slab_range(t.slab, g.kslab, g.K);
+  const int64_t k0 = kr.k0, k1 = kr.k1;
   const int nchunks = (int)((k1 - k0 + BK - 1) / BK);
 
   const int tid = threadIdx.x;
@@ -92,7 +152,7 @@ __global__ __launch_bounds__(TPB, 2) void gemm_nt_mfma_kernel(GemmArgs g) {
   const int sseg = tid & 7;             // k offset sseg*2
   // row offsets are recomputed per chunk (cheap next to 64 MFMAs) instead of keeping 8 pointers live;
   // out-of-range rows are clamped: they are computed but never stored
-  const int arow0 = tm * BM + srow, brow0 = tn * BN + srow;
+  const int arow0 = t.tm * BM + srow, brow0 = t.tn * BN + srow;
   const int mlast = g.M - 1, nlast = g.N - 1;
   const double* __restrict__ Ag = g.A;
   const double* __restrict__ Bg = g.B;
@@ -153,10 +213,6 @@ __global__ __launch_bounds__(TPB, 2) void gemm_nt_mfma_kernel(GemmArgs g) {
       AF[i] = pa[i * 16 * LDT + (KK) * 4];                                                    \
       BF[i] = pb[i * 16 * LDT + (KK) * 4];                                                    \
     }
-#define ISDF_MFMA16(AF, BF)                                                                   \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                             \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                           \
-        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[i], BF[j], acc[i][j], 0, 0, 0);
     ISDF_FRAGS(0, a0, b0)
     ISDF_FRAGS(1, a1, b1)
     ISDF_MFMA16(a0, b0)
@@ -168,26 +224,13 @@ __global__ __launch_bounds__(TPB, 2) void gemm_nt_mfma_kernel(GemmArgs g) {
     if (c + 1 < nchunks) ISDF_STORE_CHUNK(buf ^ 1)
     __syncthreads();
   }
-
-  // epilogue: D[row = (lane>>4) + 4r][col = lane&15] per 16x16 accumulator
-  double* out = g.P + (int64_t)slab * g.slab_stride;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = tm * BM + wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-      if (row >= g.M) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = tn * BN + wn * 64 + j * 16 + (lane & 15);
-        if (col >= g.N) continue;
-        double* q = out + (int64_t)row * g.ldp + col;
-        const double v = acc[i][j][r];
-        if (g.direct) *q = (g.beta == 0.0) ? g.alpha * v : g.alpha * v + g.beta * (*q);
-        else *q = v;
-      }
-    }
-  }
+  double* out = g.P + (int64_t)t.slab * g.slab_stride;
+  ISDF_STORE_ACC(4, 4, t.tm * BM + wm * 64, t.tn * BN + wn * 64, g.M, g.N, ISDF_SLAB_STORE)
+#undef ISDF_LOAD_ONE
+#undef ISDF_LOAD_CHUNK
+#undef ISDF_STORE_ONE
+#undef ISDF_STORE_CHUNK
+#undef ISDF_FRAGS
 }
 
 // ---- variant B: 256x128 tile, 8 waves (one workgroup per CU), operand loads two chunks ahead ------
@@ -199,21 +242,139 @@ __global__ __launch_bounds__(TPB, 2) void gemm_nt_mfma_kernel(GemmArgs g) {
 constexpr int BM2 = 256;
 constexpr int TPB2 = 512;
 
+// One work unit of variant B: output tile (tm, tn) of A (M rows) times B^T (N rows), both with K contiguous, over nchunks
+// 16-deep chunks from k0, into acc (the wave's 64 x 64 part: 4 x 2 waves, see ISDF_STORE_ACC).  Aligned path only: an even
+// number of chunks, 16-byte aligned rows.  No conditionals in the main loop: the tail re-loads the last chunk.
+// smem: [2][BM2*LDT] A | [2][BN*LDT] B.
 template <bool SCALED>
-__global__ __launch_bounds__(TPB2, 2) void gemm_nt_mfma_kernel_b(GemmArgs g) {
-  // aligned path only: K % 32 == 0, kslab % 32 == 0 (an even number of 16-deep chunks per slab),
-  // 16-byte aligned rows.  No conditionals in the main loop: the tail re-loads the last chunk.
-  extern __shared__ double smem[];                      // [2][BM2*LDT] A | [2][BN*LDT] B
+__device__ __forceinline__ void tile_256x128(const double* A, int64_t lda, const double* B, int64_t ldb, const double* kscale,
+                                             int M, int N, int tm, int tn, int64_t k0, int nchunks, double* smem, d4 (&acc)[4][4]) {
   double* sA = smem;
   double* sB = smem + 2 * BM2 * LDT;
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = g.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int last = nchunks - 1;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;              // 4 x 2 waves, 64x64 each
+  const int srow = tid >> 3;                            // 0..63
+  const int sseg = tid & 7;
+  const int mlast = M - 1, nlast = N - 1;
+  // six row pointers (A: rows srow + 64 i, B: rows srow + 64 i), clamped at the matrix edge
+  const double* pA0 = A + (int64_t)min(tm * BM2 + srow, mlast) * lda + k0 + sseg * 2;
+  const double* pA1 = A + (int64_t)min(tm * BM2 + srow + 64, mlast) * lda + k0 + sseg * 2;
+  const double* pA2 = A + (int64_t)min(tm * BM2 + srow + 128, mlast) * lda + k0 + sseg * 2;
+  const double* pA3 = A + (int64_t)min(tm * BM2 + srow + 192, mlast) * lda + k0 + sseg * 2;
+  const double* pB0 = B + (int64_t)min(tn * BN + srow, nlast) * ldb + k0 + sseg * 2;
+  const double* pB1 = B + (int64_t)min(tn * BN + srow + 64, nlast) * ldb + k0 + sseg * 2;
+  const double* pS = SCALED ? kscale + k0 + sseg * 2 : nullptr;
+
+  // staging registers as named scalars (arrays captured by helpers ended up in scratch)
+  double2 xa0, xa1, xa2, xa3, xb0, xb1, ya0, ya1, ya2, ya3, yb0, yb1;
+#define ISDF_LOADB(C, A0, A1, A2, A3, B0, B1)                                                 \
+  {                                                                                           \
+    const int off = (C) * BK;                                                                 \
+    A0 = *reinterpret_cast<const double2*>(pA0 + off);                                        \
+    A1 = *reinterpret_cast<const double2*>(pA1 + off);                                        \
+    A2 = *reinterpret_cast<const double2*>(pA2 + off);                                        \
+    A3 = *reinterpret_cast<const double2*>(pA3 + off);                                        \
+    B0 = *reinterpret_cast<const double2*>(pB0 + off);                                        \
+    B1 = *reinterpret_cast<const double2*>(pB1 + off);                                        \
+    if (SCALED) {                                                                             \
+      const double2 sc = *reinterpret_cast<const double2*>(pS + off);                         \
+      B0.x *= sc.x; B0.y *= sc.y; B1.x *= sc.x; B1.y *= sc.y;                                 \
+    }                                                                                         \
+  }
+#define ISDF_ST1(P, R) { double* q_ = (P); q_[0] = R.x; q_[1] = R.y; }
+#define ISDF_STOREB(BUF, A0, A1, A2, A3, B0, B1)                                              \
+  {                                                                                           \
+    double* qa = sA + (BUF) * BM2 * LDT + srow * LDT + sseg * 2;                              \
+    double* qb = sB + (BUF) * BN * LDT + srow * LDT + sseg * 2;                               \
+    ISDF_ST1(qa, A0) ISDF_ST1(qa + 64 * LDT, A1) ISDF_ST1(qa + 128 * LDT, A2)                 \
+    ISDF_ST1(qa + 192 * LDT, A3) ISDF_ST1(qb, B0) ISDF_ST1(qb + 64 * LDT, B1)                 \
+  }
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+  const int frow = lane & 15, fk = lane >> 4;
+
+  // exactly two fragment sets live (the scheduler would otherwise hoist all four k-steps' reads and
+  // spill): reads of k-step kk+1 are issued before the MFMAs of kk, fenced by sched_barrier
+  // One chunk = four k-steps.  Fragment sets alternate (k0: set 0, k1: set 1, k2: set 0, k3: set 1); each region issues
+  // the LDS reads of the NEXT k-step under its own MFMAs (ISDF_ISSUE); the six global loads of the chunk after next ride
+  // along in the first k-step and the LDS writes of the next chunk in the third.  The chunk's single barrier sits after
+  // k-step 2: by then every wave has issued and completed (s_waitcnt in __syncthreads) all its reads of the current buffer
+  // and has written its part of the next one, so k-step 3 can already prefetch the first fragments of the next chunk from
+  // the other buffer and the MFMA stream runs across the chunk boundary without the post-barrier bubble.  A wave can only
+  // reach the next chunk's writes of this buffer after passing this barrier, i.e. after all waves finished reading it.
+  const int aoff = (wm * 64 + frow) * LDT + fk, boff = (wn * 64 + frow) * LDT + fk;
+  double a0[4], b0[4], a1[4], b1[4];
+#define ISDF_FRAGQ(BUF, KK, AF, BF)                                                           \
+  {                                                                                           \
+    const double* pa = sA + (BUF) * BM2 * LDT + aoff;                                         \
+    const double* pb = sB + (BUF) * BN * LDT + boff;                                          \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                           \
+      AF[i] = pa[i * 16 * LDT + (KK) * 4];                                                    \
+      BF[i] = pb[i * 16 * LDT + (KK) * 4];                                                    \
+    }                                                                                         \
+  }
+#define ISDF_CHUNKB(BUF, LOAD_AHEAD, STORE_NEXT)                                              \
+  {                                                                                           \
+    ISDF_FRAGQ(BUF, 1, a1, b1)                                                                \
+    LOAD_AHEAD                                                                                \
+    ISDF_MFMA16(a0, b0)                                                                       \
+    ISDF_ISSUE(0x020, 6)                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    ISDF_FRAGQ(BUF, 2, a0, b0)                                                                \
+    ISDF_MFMA16(a1, b1)                                                                       \
+    ISDF_ISSUE(0, 0)                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    ISDF_FRAGQ(BUF, 3, a1, b1)                                                                \
+    STORE_NEXT                                                                                \
+    ISDF_MFMA16(a0, b0)                                                                       \
+    ISDF_ISSUE(0x200, 6)                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    __syncthreads();                                                                          \
+    ISDF_FRAGQ(1 - (BUF), 0, a0, b0)                                                          \
+    ISDF_MFMA16(a1, b1)                                                                       \
+    ISDF_ISSUE(0, 0)                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+  }
+
+  // prologue: chunk 0 -> LDS buffer 0; chunk 1 in flight in set Y; first fragments of chunk 0
+  ISDF_LOADB(0, xa0, xa1, xa2, xa3, xb0, xb1)
+  ISDF_LOADB(1, ya0, ya1, ya2, ya3, yb0, yb1)
+  ISDF_STOREB(0, xa0, xa1, xa2, xa3, xb0, xb1)
+  __syncthreads();
+  ISDF_FRAGQ(0, 0, a0, b0)
+  __builtin_amdgcn_sched_barrier(0);
+  // steady state, two chunks per iteration: while chunk c computes, chunk c+1 sits in registers and
+  // chunk c+2 is being loaded, so every load has two chunks of MFMAs to land
+  for (int c = 0; c < nchunks; c += 2) {
+    ISDF_CHUNKB(0, ISDF_LOADB(min(c + 2, last), xa0, xa1, xa2, xa3, xb0, xb1), ISDF_STOREB(1, ya0, ya1, ya2, ya3, yb0, yb1))
+    ISDF_CHUNKB(1, ISDF_LOADB(min(c + 3, last), ya0, ya1, ya2, ya3, yb0, yb1), ISDF_STOREB(0, xa0, xa1, xa2, xa3, xb0, xb1))
+  }
+#undef ISDF_LOADB
+#undef ISDF_ST1
+#undef ISDF_STOREB
+#undef ISDF_FRAGQ
+#undef ISDF_CHUNKB
+}
+
+template <bool SCALED>
+__global__ __launch_bounds__(TPB2, 2) void gemm_nt_mfma_kernel_b(GemmArgs g) {
+  // K % 32 == 0, kslab % 32 == 0: an even number of 16-deep chunks per slab
+  extern __shared__ double smem[];
+  const int64_t unit = xcd_unit(g.nunits_pad);
   if (unit >= g.nunits) return;
-  const int tm = (int)(unit % g.ntm);
-  const int tn = (int)((unit / g.ntm) % g.ntn);
-  const int slab = (int)(unit / ((int64_t)g.ntm * g.ntn));
-#include "gemm_nt_b_unit.inc"
+  const Tile t = decode_tile(unit, g.ntm, g.ntn);
+  const KRange kr = slab_range(t.slab, g.kslab, g.K);
+  d4 acc[4][4];
+  tile_256x128<SCALED>(g.A, g.lda, g.B, g.ldb, g.kscale, g.M, g.N, t.tm, t.tn, kr.k0, (int)((kr.k1 - kr.k0) / BK), smem, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* out = g.P + (int64_t)t.slab * g.slab_stride;
+  ISDF_STORE_ACC(4, 4, t.tm * BM2 + (wave >> 1) * 64, t.tn * BN + (wave & 1) * 64, g.M, g.N, ISDF_SLAB_STORE)
 }
 
 // ---- grouped block-lower Gram triangles S_b = X_b X_b^T for the candidate selection (select_ip.hip) -----------------------
@@ -233,28 +394,19 @@ struct GramTriArgs {
 
 __global__ __launch_bounds__(TPB2, 2) void gram_tri_mfma_kernel(GramTriArgs t) {
   extern __shared__ double smem[];
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = t.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int64_t unit = xcd_unit(t.nunits_pad);
   if (unit >= t.nunits) return;
   const GramTriUnit u = t.units[unit];
   const int64_t r0 = t.blk_off[u.blk];
-  GemmArgs g;
-  g.A = g.B = t.X + (r0 - t.row0) * t.ldx;
-  g.lda = g.ldb = t.ldx;
-  g.kscale = nullptr;
-  g.M = g.N = (int)(t.blk_off[u.blk + 1] - r0);
-  g.K = g.kslab = t.K;
+  const double* X = t.X + (r0 - t.row0) * t.ldx;
+  const int m = (int)(t.blk_off[u.blk + 1] - r0);
   // row r of the tile row sits at gram_tri_row(r) = gram_tri_row(256 tm) + (r - 256 tm) * ldp: the unit addresses rows by r
-  g.ldp = (int64_t)(u.tm + 1) * BM2;
-  g.P = t.S + t.tri_off[u.blk] + (gram_tri_row((int64_t)u.tm * BM2) - (int64_t)u.tm * BM2 * g.ldp);
-  g.slab_stride = 0;
-  g.direct = 1; g.alpha = 1.0; g.beta = 0.0;
-  constexpr bool SCALED = false;
-  double* sA = smem;
-  double* sB = smem + 2 * BM2 * LDT;
-  const int tm = u.tm, tn = u.tn, slab = 0;
-#include "gemm_nt_b_unit.inc"
+  const int64_t ldp = (int64_t)(u.tm + 1) * BM2;
+  double* S = t.S + t.tri_off[u.blk] + (gram_tri_row((int64_t)u.tm * BM2) - (int64_t)u.tm * BM2 * ldp);
+  d4 acc[4][4];
+  tile_256x128<false>(X, t.ldx, X, t.ldx, nullptr, m, m, u.tm, u.tn, 0, t.K / BK, smem, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  ISDF_STORE_ACC(4, 4, u.tm * BM2 + (wave >> 1) * 64, u.tn * BN + (wave & 1) * 64, m, m, S[(int64_t)row * ldp + col] = acc[i][j][r];)
 }
 
 // ---- variant D: A straight from global memory into MFMA operand registers, only B through LDS ----------------------
@@ -270,16 +422,13 @@ constexpr int TPBD = 256;
 template <bool SCALED>
 __global__ __launch_bounds__(TPBD, 2) void gemm_nt_mfma_kernel_d(GemmArgs g) {
   __shared__ double sB[2][BN * LDT];
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = g.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int64_t unit = xcd_unit(g.nunits_pad);
   if (unit >= g.nunits) return;
-  const int tm = (int)(unit % g.ntm);
-  const int tn = (int)((unit / g.ntm) % g.ntn);
-  const int slab = (int)(unit / ((int64_t)g.ntm * g.ntn));
-  const int64_t k0 = (int64_t)slab * g.kslab;
-  const int64_t k1 = (k0 + g.kslab < g.K) ? k0 + g.kslab : g.K;
-  const int nchunks = (int)((k1 - k0) / BK);            // even (kslab is a multiple of 2 BK, K % 32 == 0)
+  const Tile t = decode_tile(unit, g.ntm, g.ntn);
+  const int tm = t.tm, tn = t.tn;
+  const KRange kr = slab_range(t.slab, g.kslab, g.K);
+  const int64_t k0 = kr.k0;
+  const int nchunks = (int)((kr.k1 - k0) / BK);         // even (kslab is a multiple of 2 BK, K % 32 == 0)
   const int last = nchunks - 1;
 
   const int tid = threadIdx.x;
@@ -344,34 +493,26 @@ __global__ __launch_bounds__(TPBD, 2) void gemm_nt_mfma_kernel_d(GemmArgs g) {
       acc[0][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(AV0, BF[jn], acc[0][jn], 0, 0, 0);    \
       acc[1][jn] = __builtin_amdgcn_mfma_f64_16x16x4f64(AV1, BF[jn], acc[1][jn], 0, 0, 0);    \
     }
-#define ISDF_ILD_R() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                       \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-#define ISDF_ILD_RL() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                      \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
-    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-#define ISDF_ILD_RW() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                      \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
-    if (q_ < 4) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
 #define ISDF_CHUNKD(BUF, A00, A01, A10, A11, LOAD_AHEAD, STORE_NEXT)                          \
   {                                                                                           \
     ISDF_FRAGD(BUF, 1, bf1)                                                                   \
     ISDF_MFMAD(A00.x, A10.x, bf0)                                                             \
-    ISDF_ILD_R()                                                                              \
+    ISDF_ISSUE(0, 0)                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     ISDF_FRAGD(BUF, 2, bf0)                                                                   \
     ISDF_MFMAD(A00.y, A10.y, bf1)                                                             \
-    ISDF_ILD_R()                                                                              \
+    ISDF_ISSUE(0, 0)                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     ISDF_FRAGD(BUF, 3, bf1)                                                                   \
     STORE_NEXT                                                                                \
     ISDF_MFMAD(A01.x, A11.x, bf0)                                                             \
-    ISDF_ILD_RW()                                                                             \
+    ISDF_ISSUE(0x200, 4)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     __syncthreads();                                                                          \
     ISDF_FRAGD(1 - (BUF), 0, bf0)                                                             \
     ISDF_MFMAD(A01.y, A11.y, bf1)                                                             \
     LOAD_AHEAD                                                                                \
-    ISDF_ILD_RL()                                                                             \
+    ISDF_ISSUE(0x020, 8)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                        \
   }
 
@@ -390,25 +531,13 @@ __global__ __launch_bounds__(TPBD, 2) void gemm_nt_mfma_kernel_d(GemmArgs g) {
     ISDF_CHUNKD(1, ya00, ya01, ya10, ya11, ISDF_LOADD(min(c + 3, last), ya00, ya01, ya10, ya11, yb00, yb01, yb10, yb11),
                 ISDF_STORED(0, xb00, xb01, xb10, xb11))
   }
-
-  double* out = g.P + (int64_t)slab * g.slab_stride;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = tm * BM + wave * 32 + i * 16 + (lane >> 4) + 4 * r;
-      if (row >= g.M) continue;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int col = tn * BN + j * 16 + (lane & 15);
-        if (col >= g.N) continue;
-        double* q = out + (int64_t)row * g.ldp + col;
-        const double v = acc[i][j][r];
-        if (g.direct) *q = (g.beta == 0.0) ? g.alpha * v : g.alpha * v + g.beta * (*q);
-        else *q = v;
-      }
-    }
-  }
+  double* out = g.P + (int64_t)t.slab * g.slab_stride;
+  ISDF_STORE_ACC(2, 8, tm * BM + wave * 32, tn * BN, g.M, g.N, ISDF_SLAB_STORE)
+#undef ISDF_LOADD
+#undef ISDF_STORED
+#undef ISDF_FRAGD
+#undef ISDF_MFMAD
+#undef ISDF_CHUNKD
 }
 
 // ---- NN form: C = A B (optionally squared element-wise), A (M x K) with K contiguous, B (K x N) with N contiguous, K short
@@ -430,20 +559,23 @@ struct GemmNNArgs {
   int64_t nunits, nunits_pad;
 };
 
+// super-tiles M-fastest, tiles M-fastest inside one; the tiles of a ragged super-tile past the edge do not exist
+__device__ __forceinline__ Tile decode_supertile(int64_t unit, const GemmNNArgs& g) {
+  const int per = g.stm * g.stn;
+  const int64_t grp = unit / per;
+  const int within = (int)(unit - grp * per);
+  return {(int)(grp % g.ngm) * g.stm + within % g.stm, (int)(grp / g.ngm) * g.stn + within / g.stm, 0};
+}
+
 template <bool SQ>
 __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
   extern __shared__ double smem[];                      // [2][BM2*LDT] A | [2][BK*LDN] B
   double* sA = smem;
   double* sB = smem + 2 * BM2 * LDT;
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = g.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int64_t unit = xcd_unit(g.nunits_pad);
   if (unit >= g.nunits) return;
-  const int per = g.stm * g.stn;
-  const int64_t grp = unit / per;
-  const int within = (int)(unit - grp * per);
-  const int tm = (int)(grp % g.ngm) * g.stm + within % g.stm;
-  const int tn = (int)(grp / g.ngm) * g.stn + within / g.stm;
+  const Tile t = decode_supertile(unit, g);
+  const int tm = t.tm, tn = t.tn;
   if (tm >= g.ntm || tn >= g.ntn) return;
   const int nchunks = g.K / BK;                         // even
   const int last = nchunks - 1;
@@ -503,40 +635,27 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
       BF[i] = pb[(KK) * 4 * LDN + i * 16];                                                    \
     }                                                                                         \
   }
-#define ISDF_NN_MFMA(AF, BF)                                                                  \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                             \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                           \
-        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(AF[i], BF[j], acc[i][j], 0, 0, 0);
-  // same issue order as variant B (see there): LDS reads / writes / global loads trickle in after every second MFMA, one
-  // barrier per chunk after k-step 2, the next chunk's first fragments prefetched under k-step 3
-#define ISDF_NN_IL() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                       \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-#define ISDF_NN_IL_L() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                     \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
-    if (q_ < 6) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-#define ISDF_NN_IL_RW() _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) {                    \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
-    if (q_ < 6) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0); }
+  // same issue order as variant B (see tile_256x128)
 #define ISDF_NN_CHUNK(BUF, LOAD_AHEAD, STORE_NEXT)                                            \
   {                                                                                           \
     ISDF_NN_FRAG(BUF, 1, a1, b1)                                                              \
     LOAD_AHEAD                                                                                \
-    ISDF_NN_MFMA(a0, b0)                                                                      \
-    ISDF_NN_IL_L()                                                                            \
+    ISDF_MFMA16(a0, b0)                                                                       \
+    ISDF_ISSUE(0x020, 6)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     ISDF_NN_FRAG(BUF, 2, a0, b0)                                                              \
-    ISDF_NN_MFMA(a1, b1)                                                                      \
-    ISDF_NN_IL()                                                                              \
+    ISDF_MFMA16(a1, b1)                                                                       \
+    ISDF_ISSUE(0, 0)                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     ISDF_NN_FRAG(BUF, 3, a1, b1)                                                              \
     STORE_NEXT                                                                                \
-    ISDF_NN_MFMA(a0, b0)                                                                      \
-    ISDF_NN_IL_RW()                                                                           \
+    ISDF_MFMA16(a0, b0)                                                                       \
+    ISDF_ISSUE(0x200, 6)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     __syncthreads();                                                                          \
     ISDF_NN_FRAG(1 - (BUF), 0, a0, b0)                                                        \
-    ISDF_NN_MFMA(a1, b1)                                                                      \
-    ISDF_NN_IL()                                                                              \
+    ISDF_MFMA16(a1, b1)                                                                       \
+    ISDF_ISSUE(0, 0)                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                        \
   }
 
@@ -550,23 +669,16 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
     ISDF_NN_CHUNK(0, ISDF_NN_LOAD(min(c + 2, last), xa0, xa1, xa2, xa3, xb0, xb1), ISDF_NN_STORE(1, ya0, ya1, ya2, ya3, yb0, yb1))
     ISDF_NN_CHUNK(1, ISDF_NN_LOAD(min(c + 3, last), ya0, ya1, ya2, ya3, yb0, yb1), ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1))
   }
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = tm * BM2 + wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-      if (row >= g.M) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = tn * BN + wn * 64 + j * 16 + (lane & 15);
-        if (col >= g.N) continue;
-        const double v = acc[i][j][r];
-        g.C[(int64_t)row * g.ldc + col] = SQ ? v * v : v;
-      }
-    }
-  }
+  ISDF_STORE_ACC(4, 4, tm * BM2 + wm * 64, tn * BN + wn * 64, g.M, g.N,
+                 { const double v = acc[i][j][r]; g.C[(int64_t)row * g.ldc + col] = SQ ? v * v : v; })
+#undef ISDF_NN_LOAD
+#undef ISDF_NN_ST1
+#undef ISDF_NN_STORE
+#undef ISDF_NN_FRAG
+#undef ISDF_NN_CHUNK
 }
+#undef ISDF_MFMA16
+#undef ISDF_ISSUE
 
 __global__ void reduce_slabs_kernel(const double* __restrict__ P, int nslab, int64_t slab_stride,
                                     int M, int N, double alpha, double beta, double* __restrict__ C,
@@ -611,16 +723,13 @@ __global__ __launch_bounds__(TPBH, 2) void herm_kscale_nt_kernel(HermArgs g) {
   double* sA = smem;
   double* sB = smem + 2 * BM * LDT;
   double* sT = smem + 2 * (BM + BN) * LDT;
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = g.nunits_pad / 8;
-  const int64_t unit = (bid % 8) * per_xcd + bid / 8;
+  const int64_t unit = xcd_unit(g.nunits_pad);
   if (unit >= g.nunits) return;
-  const int tm = (int)(unit % g.ntm);
-  const int tn = (int)((unit / g.ntm) % g.ntn);
-  const int slab = (int)(unit / ((int64_t)g.ntm * g.ntn));
-  const int64_t k0 = (int64_t)slab * g.kslab;
-  const int64_t k1 = (k0 + g.kslab < g.K) ? k0 + g.kslab : g.K;
-  const int nchunks = (int)((k1 - k0) / BK);
+  const Tile t = decode_tile(unit, g.ntm, g.ntn);
+  const int tm = t.tm, tn = t.tn, slab = t.slab;
+  const KRange kr = slab_range(slab, g.kslab, g.K);
+  const int64_t k0 = kr.k0;
+  const int nchunks = (int)((kr.k1 - k0) / BK);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -701,28 +810,70 @@ __global__ __launch_bounds__(TPBH, 2) void herm_kscale_nt_kernel(HermArgs g) {
 
   double* ore = g.Pre + (int64_t)slab * g.slab_stride;
   double* oim = g.Pim + (int64_t)slab * g.slab_stride;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = tm * BM + wm * 64 + i * 16 + (lane >> 4) + 4 * r;
-      if (row >= g.M) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = tn * BN + wn * 32 + j * 16 + (lane & 15);
-        if (col >= g.N) continue;
-        const int64_t o = (int64_t)row * g.ldp + col;
-        const double vr = cre[i][j][r], vi = cim[i][j][r];
-        if (g.direct) {
-          ore[o] = (g.beta == 0.0) ? g.alpha * vr : g.alpha * vr + g.beta * ore[o];
-          oim[o] = (g.beta == 0.0) ? g.alpha * vi : g.alpha * vi + g.beta * oim[o];
-        } else {
-          ore[o] = vr;
-          oim[o] = vi;
-        }
-      }
-    }
+#define ISDF_HERM_STORE                                                                       \
+  {                                                                                           \
+    const int64_t o = (int64_t)row * g.ldp + col;                                             \
+    const double vr = cre[i][j][r], vi = cim[i][j][r];                                        \
+    if (g.direct) {                                                                           \
+      ore[o] = (g.beta == 0.0) ? g.alpha * vr : g.alpha * vr + g.beta * ore[o];               \
+      oim[o] = (g.beta == 0.0) ? g.alpha * vi : g.alpha * vi + g.beta * oim[o];               \
+    } else {                                                                                  \
+      ore[o] = vr;                                                                            \
+      oim[o] = vi;                                                                            \
+    }                                                                                         \
   }
+  ISDF_STORE_ACC(4, 2, tm * BM + wm * 64, tn * BN + wn * 32, g.M, g.N, ISDF_HERM_STORE)
+#undef ISDF_HERM_STORE
+#undef ISDF_LOADH
+#undef ISDF_STH
+#undef ISDF_STOREH
+}
+#undef ISDF_STORE_ACC
+#undef ISDF_SLAB_STORE
+
+// ---- host side: slab plan, operand alignment, dynamic LDS -------------------------------------------------------------------------------
+struct SlabPlan { int nslab; int64_t kslab, nunits, nunits_pad; };
+
+// K slabs of an NT product of ntiles output tiles on `slots` resident workgroups: enough units to fill the slots about 8 times
+// over, slabs at least 2048 deep, partial workspace (out_bytes per entry of the M x N output) at most 2 GiB, slab length a
+// multiple of kmult.
+// tune = wave quantisation: the units are dealt to `slots` resident workgroups, so the launch takes ceil(units / slots) unit
+// times.  Among slab counts between the target and twice the target pick the one whose last round is fullest
+// (512 x 15132 output: 238 tiles; 9 slabs = 8.37 rounds -> 9, 15 slabs = 13.95 rounds -> 14: 7 % less idle time)
+SlabPlan plan_slabs(int64_t ntiles, int64_t slots, int M, int N, int64_t K, int out_bytes, int kmult, bool tune) {
+  int64_t nslab = cdiv(8 * slots, ntiles);
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(1, K / 2048),
+                                                             std::max<int64_t>(1, ((int64_t)2 << 30) / ((int64_t)M * N * out_bytes))));
+  nslab = std::max<int64_t>(1, std::min<int64_t>(nslab, cap));
+  if (tune && ntiles * nslab > slots) {
+    double best = 1e30;
+    int64_t pick = nslab;
+    for (int64_t c = nslab; c <= std::min<int64_t>(2 * nslab, cap); ++c) {
+      const double units = (double)ntiles * c;
+      const double waste = (double)(cdiv((int64_t)units, slots) * slots) / units;
+      if (waste < best - 1e-9) { best = waste; pick = c; }
+    }
+    nslab = pick;
+  }
+  SlabPlan p;
+  p.kslab = cdiv(cdiv(K, nslab), kmult) * kmult;
+  p.nslab = (int)cdiv(K, p.kslab);
+  p.nunits = ntiles * p.nslab;
+  p.nunits_pad = cdiv(p.nunits, 8) * 8;
+  return p;
+}
+
+// rows of ld doubles from p start on 16-byte boundaries (ld = 0: a vector; a null pointer passes)
+bool rows_aligned16(const double* p, int64_t ld = 0) { return ld % 2 == 0 && ((uintptr_t)p) % 16 == 0; }
+
+// raise the dynamic-LDS limit of the kernels once per handle (= per device), not per process; `done` is the handle's flag
+template <class... Kernels>
+int raise_lds_once(isdf_handle h, int& done, size_t lds, Kernels... kernels) {
+  if (done) return ISDF_OK;
+  for (const void* k : {(const void*)kernels...})
+    HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  done = 1;
+  return ISDF_OK;
 }
 
 }  // namespace
@@ -733,34 +884,14 @@ extern "C" int isdf_herm_kscale_nt(isdf_handle h, int M, int N, int64_t K, doubl
                                    double* d_Cre, double* d_Cim, int64_t ldc) {
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, M > 0 && N > 0 && K > 0 && d_A && d_B && d_s && d_a && d_Cre && d_Cim && lda >= K && ldb >= K && ldc >= N);
-  ARG_CHECK(h, K % BK == 0 && lda % 2 == 0 && ldb % 2 == 0 && ((uintptr_t)d_A) % 16 == 0 && ((uintptr_t)d_B) % 16 == 0 &&
-                   ((uintptr_t)d_s) % 16 == 0 && ((uintptr_t)d_a) % 16 == 0);
+  ARG_CHECK(h, K % BK == 0 && rows_aligned16(d_A, lda) && rows_aligned16(d_B, ldb) && rows_aligned16(d_s) && rows_aligned16(d_a));
   HermArgs g;
   g.A = d_A; g.lda = lda; g.B = d_B; g.ldb = ldb; g.s = d_s; g.a = d_a;
   g.M = M; g.N = N; g.K = K;
   g.ntm = (int)cdiv(M, BM); g.ntn = (int)cdiv(N, BN);
-  const int64_t ntiles = (int64_t)g.ntm * g.ntn;
-  // one workgroup of eight waves per CU; slabs as in gemm_nt_f64_scaled: units to fill the device about 8 times over, at least
-  // 2048 deep, the two planes' partials at most 2 GiB, the slab count whose last round of units is fullest
-  const int64_t slots = (int64_t)h->num_cu;
-  int64_t nslab = cdiv(8 * slots, ntiles);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(1, K / 2048),
-                                                             std::max<int64_t>(1, ((int64_t)2 << 30) / ((int64_t)M * N * 16))));
-  nslab = std::max<int64_t>(1, std::min<int64_t>(nslab, cap));
-  if (ntiles * nslab > slots) {
-    double best = 1e30;
-    int64_t pick = nslab;
-    for (int64_t c = nslab; c <= std::min<int64_t>(2 * nslab, cap); ++c) {
-      const double units = (double)ntiles * c;
-      const double waste = (double)(cdiv((int64_t)units, slots) * slots) / units;
-      if (waste < best - 1e-9) { best = waste; pick = c; }
-    }
-    nslab = pick;
-  }
-  g.kslab = cdiv(cdiv(K, nslab), BK) * BK;
-  g.nslab = (int)cdiv(K, g.kslab);
-  g.nunits = ntiles * g.nslab;
-  g.nunits_pad = cdiv(g.nunits, 8) * 8;
+  // one workgroup of eight waves per CU; the two planes' partials share the 2 GiB
+  const SlabPlan p = plan_slabs((int64_t)g.ntm * g.ntn, h->num_cu, M, N, K, 16, BK, true);
+  g.kslab = p.kslab; g.nslab = p.nslab; g.nunits = p.nunits; g.nunits_pad = p.nunits_pad;
   ARG_CHECK(h, g.nunits_pad < 2147483647LL);
   g.alpha = alpha; g.beta = beta;
   const int64_t plane = (int64_t)M * N;
@@ -774,10 +905,7 @@ extern "C" int isdf_herm_kscale_nt(isdf_handle h, int M, int N, int64_t K, doubl
     g.ldp = N; g.slab_stride = 2 * plane;
   }
   const size_t lds = sizeof(double) * (2 * (BM + BN) * LDT + 4 * BK);
-  if (!h->attr_herm) {
-    HIP_TRY(h, hipFuncSetAttribute((const void*)herm_kscale_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->attr_herm = 1;
-  }
+  if (int rc = raise_lds_once(h, h->attr_herm, lds, herm_kscale_nt_kernel)) return rc;
   {
     ProfScope ps(h, "herm_kscale_nt_kernel[flop]", 4.0 * M * N * (double)K);
     hipLaunchKernelGGL(herm_kscale_nt_kernel, dim3((unsigned)g.nunits_pad), dim3(TPBH), lds, h->stream, g);
@@ -805,8 +933,9 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
   // variant: -1 auto (default), 0 force the 128x128 kernel, 1 force the 256x128 kernel where legal, 3 the 128x128 kernel with
   // A direct to registers (variant D) where legal
   static const int variant = getenv("ISDF_GEMM_VARIANT") ? atoi(getenv("ISDF_GEMM_VARIANT")) : -1;
-  const bool alignedB = (lda % 2 == 0) && (ldb % 2 == 0) && (K % 32 == 0) && (((uintptr_t)A) % 16 == 0) &&
-                        (((uintptr_t)B) % 16 == 0) && (!kscale || ((uintptr_t)kscale) % 16 == 0);
+  static const int tune = getenv("ISDF_GEMM_SLAB_TUNE") ? atoi(getenv("ISDF_GEMM_SLAB_TUNE")) : 1;
+  const bool aligned = rows_aligned16(A, lda) && rows_aligned16(B, ldb) && rows_aligned16(kscale);
+  const bool alignedB = aligned && K % 32 == 0, fast = aligned && K % BK == 0;
   // auto: the 256x128 kernel (B) whenever M fills 256-row tiles (row padding < 15 %): after the issue-order work it leads on
   // every such shape measured, the k-point W^q batches most of all (MgO 2x2x2: 3.8 s against 4.5 s with D); variant D (A
   // direct to registers, 128x128, two workgroups per CU) for the other aligned shapes, variant A for unaligned operands
@@ -814,34 +943,9 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
   const bool useB = alignedB && M > BM && (variant == 1 || (variant == -1 && fitsB));
   const bool useD = alignedB && !useB && (variant == 3 || variant == -1);
   g.ntm = (int)cdiv(M, useB ? BM2 : BM); g.ntn = (int)cdiv(N, BN);
-  const int64_t ntiles = (int64_t)g.ntm * g.ntn;
-  // enough units to fill 2 workgroups per CU about 8 times over, slabs at least 2048 deep,
-  // partial workspace at most 2 GiB
-  const int64_t slots = (int64_t)h->num_cu * (useB ? 1 : 2);
-  int64_t nslab = cdiv(8 * slots, ntiles);
-  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(1, K / 2048),
-                                                             std::max<int64_t>(1, ((int64_t)2 << 30) / ((int64_t)M * N * 8))));
-  nslab = std::max<int64_t>(1, std::min<int64_t>(nslab, cap));
-  {
-    // wave quantisation: the units are dealt to `slots` resident workgroups, so the launch takes ceil(units / slots) unit
-    // times.  Among slab counts between the target and twice the target pick the one whose last round is fullest
-    // (512 x 15132 output: 238 tiles; 9 slabs = 8.37 rounds -> 9, 15 slabs = 13.95 rounds -> 14: 7 % less idle time)
-    static const int tune = getenv("ISDF_GEMM_SLAB_TUNE") ? atoi(getenv("ISDF_GEMM_SLAB_TUNE")) : 1;
-    if (tune && ntiles * nslab > slots) {
-      double best = 1e30;
-      int64_t pick = nslab;
-      for (int64_t c = nslab; c <= std::min<int64_t>(2 * nslab, cap); ++c) {
-        const double units = (double)ntiles * c;
-        const double waste = (double)(cdiv((int64_t)units, slots) * slots) / units;
-        if (waste < best - 1e-9) { best = waste; pick = c; }
-      }
-      nslab = pick;
-    }
-  }
-  g.kslab = cdiv(cdiv(K, nslab), 2 * BK) * (2 * BK);   // even number of chunks per slab
-  g.nslab = (int)cdiv(K, g.kslab);
-  g.nunits = ntiles * g.nslab;
-  g.nunits_pad = cdiv(g.nunits, 8) * 8;
+  // 2 workgroups per CU (B: one); an even number of chunks per slab
+  const SlabPlan p = plan_slabs((int64_t)g.ntm * g.ntn, (int64_t)h->num_cu * (useB ? 1 : 2), M, N, K, 8, 2 * BK, tune != 0);
+  g.kslab = p.kslab; g.nslab = p.nslab; g.nunits = p.nunits; g.nunits_pad = p.nunits_pad;
   g.alpha = alpha; g.beta = beta;
   if (g.nslab == 1) {
     g.direct = 1; g.P = C; g.ldp = ldc; g.slab_stride = 0;
@@ -851,9 +955,6 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
     if (!g.P) return ISDF_ERR_HIP;
     g.ldp = N; g.slab_stride = (int64_t)M * N;
   }
-  const bool fast = (lda % 2 == 0) && (ldb % 2 == 0) && (K % BK == 0) &&
-                    (((uintptr_t)A) % 16 == 0) && (((uintptr_t)B) % 16 == 0) &&
-                    (!kscale || ((uintptr_t)kscale) % 16 == 0);
   ARG_CHECK(h, g.nunits_pad < 2147483647LL);
   // one profiling label per kernel instantiation, named as rocprofv3 names them
   const char* label = useD ? (kscale ? "gemm_nt_mfma_kernel_d<true>[flop]" : "gemm_nt_mfma_kernel_d<false>[flop]") : useB ? (kscale ? "gemm_nt_mfma_kernel_b<true>[flop]" : "gemm_nt_mfma_kernel_b<false>[flop]")
@@ -865,11 +966,7 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
       else hipLaunchKernelGGL(gemm_nt_mfma_kernel_d<false>, dim3((unsigned)g.nunits_pad), dim3(TPBD), 0, h->stream, g);
     } else if (useB) {
       const size_t lds = sizeof(double) * 2 * (BM2 + BN) * LDT;
-      if (!h->attr_gemm_b) {                       // per handle (= per device), not per process
-        HIP_TRY(h, hipFuncSetAttribute((const void*)gemm_nt_mfma_kernel_b<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)gemm_nt_mfma_kernel_b<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->attr_gemm_b = 1;
-      }
+      if (int rc = raise_lds_once(h, h->attr_gemm_b, lds, gemm_nt_mfma_kernel_b<true>, gemm_nt_mfma_kernel_b<false>)) return rc;
       if (kscale) hipLaunchKernelGGL(gemm_nt_mfma_kernel_b<true>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
       else hipLaunchKernelGGL(gemm_nt_mfma_kernel_b<false>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
     } else if (fast) hipLaunchKernelGGL(gemm_nt_mfma_kernel<true>, dim3((unsigned)g.nunits_pad), dim3(TPB), 0, h->stream, g);
@@ -900,17 +997,14 @@ extern "C" int isdf_gemm_nt(isdf_handle h, int M, int N, int64_t K, double alpha
 
 int gram_tri_blocks(isdf_handle h, const double* X, int64_t ldx, int K, const GramTriUnit* d_units, int64_t nunits,
                     const int64_t* d_blk_off, int64_t row0, const int64_t* d_tri_off, double* S, double flop) {
-  ARG_CHECK(h, X && d_units && d_blk_off && d_tri_off && S && nunits > 0 && K > 0 && K % 32 == 0 && ldx >= K && ldx % 2 == 0 &&
-                   ((uintptr_t)X) % 16 == 0);
+  ARG_CHECK(h, X && d_units && d_blk_off && d_tri_off && S && nunits > 0 && K > 0 && K % 32 == 0 && ldx >= K &&
+                   rows_aligned16(X, ldx));
   GramTriArgs t;
   t.X = X; t.ldx = ldx; t.K = K; t.units = d_units; t.blk_off = d_blk_off; t.row0 = row0; t.tri_off = d_tri_off; t.S = S;
   t.nunits = nunits; t.nunits_pad = cdiv(nunits, 8) * 8;
   ARG_CHECK(h, t.nunits_pad < 2147483647LL);
   const size_t lds = sizeof(double) * 2 * (BM2 + BN) * LDT;
-  if (!h->attr_gram_tri) {
-    HIP_TRY(h, hipFuncSetAttribute((const void*)gram_tri_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->attr_gram_tri = 1;
-  }
+  if (int rc = raise_lds_once(h, h->attr_gram_tri, lds, gram_tri_mfma_kernel)) return rc;
   ProfScope ps(h, "cand_gram_blocks[flop]", flop);
   hipLaunchKernelGGL(gram_tri_mfma_kernel, dim3((unsigned)t.nunits_pad), dim3(TPB2), lds, h->stream, t);
   KERNEL_CHECK(h);
@@ -923,8 +1017,7 @@ bool gemm_nn_f64_supported(isdf_handle h, int64_t M, int64_t N, int64_t K, const
   // alone and 66 TF/s inside the build, rocBLAS 74-75 and 74 (profiles/r02_gemm_nn_vs_rocblas.log) - the library keeps this
   // product by default
   return h->gemm_nn_own && M > BM && (double)(cdiv(M, BM2) * BM2) <= 1.15 * (double)M && N >= 2 && N % 2 == 0 && K >= 32 && K % 32 == 0 &&
-         lda % 2 == 0 && ldb % 2 == 0 && ((uintptr_t)A) % 16 == 0 && ((uintptr_t)B) % 16 == 0 && M < 2147483647LL &&
-         N < 2147483647LL && K < 2147483647LL;
+         rows_aligned16(A, lda) && rows_aligned16(B, ldb) && M < 2147483647LL && N < 2147483647LL && K < 2147483647LL;
 }
 
 int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -941,11 +1034,7 @@ int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A,
   g.nunits_pad = cdiv(g.nunits, 8) * 8;
   ARG_CHECK(h, g.nunits_pad < 2147483647LL);
   const size_t lds = sizeof(double) * 2 * (BM2 * LDT + BK * LDN);
-  if (!h->attr_gemm_nn) {
-    HIP_TRY(h, hipFuncSetAttribute((const void*)gemm_nn_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(h, hipFuncSetAttribute((const void*)gemm_nn_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->attr_gemm_nn = 1;
-  }
+  if (int rc = raise_lds_once(h, h->attr_gemm_nn, lds, gemm_nn_mfma_kernel<true>, gemm_nn_mfma_kernel<false>)) return rc;
   ProfScope ps(h, square ? "gemm_nn_mfma_kernel<true>[flop]" : "gemm_nn_mfma_kernel<false>[flop]", 2.0 * M * N * (double)K);
   if (square) hipLaunchKernelGGL(gemm_nn_mfma_kernel<true>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
   else hipLaunchKernelGGL(gemm_nn_mfma_kernel<false>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);

@@ -1,4 +1,4 @@
-"""Sweep of the hand-written FP64 matrix-core products (csrc/gemm_f64.hip, gemm_nt_b_unit.inc) over every kernel, edge and stride.
+"""Sweep of the hand-written FP64 matrix-core products (csrc/gemm_f64.hip) over every kernel, edge and stride.
 
 The older GEMM tests (test_gpu_parity.py: test_gemm_nt_mfma, test_gemm_nn_mfma, test_pair_gram_rows_squared_epilogue;
 test_gpu_kpts_spectral.py: test_herm_kscale_nt_matches_numpy_and_the_gemm_composition) use a few contiguous, aligned shapes with
