@@ -107,7 +107,7 @@ def smooth(seq):
 
 
 def plane_lds_bytes(n1, n2):
-    """LDS bytes of the real (y, z) plane pass, 0 when the plane does not fit (plane_lds_bytes)."""
+    """LDS bytes of the real (y, z) plane pass, 0 when the plane does not fit (plane_geometry, real form)."""
     n2h, npair = n2 // 2 + 1, (n1 + 1) // 2
     Lz = npair
     while Lz % 16 != 1:
@@ -120,7 +120,7 @@ def plane_lds_bytes(n1, n2):
 
 
 def plane_c2c_lds_bytes(n1, n2):
-    """LDS bytes of the complex plane pass of the k-point form, 0 when it does not fit (plane_c2c_lds_bytes)."""
+    """LDS bytes of the complex plane pass of the k-point form, 0 when it does not fit (plane_geometry, complex form)."""
     if n1 * n2 > PLANE_ENTRIES:
         return 0
     Lz = n1

@@ -172,8 +172,8 @@ def test_occupied_orbitals_of_a_density_matrix():
 def test_fft_float_reciprocal_index_split_is_exact():
     """The plane and FAST kernels of csrc/fft_conv.hip split a flat index c into (c / n, c % n) through a single-precision
     reciprocal, ``l = (int)(((float)c + 0.5f) * inv_n)`` with ``inv_n = 1.0f / (float)n`` (the loads, separations and stores of
-    z_r2c_fast_kernel / z_c2r_fast_kernel, plane_fwd_kernel / plane_inv_kernel, their pipelined forms and plane_c2c_inv_kernel,
-    with n = n2, n2 / 2 + 1; the butterfly index of stage_inplace / stage_plane with n = the stage stride and the line count).
+    z_r2c_fast_kernel / z_c2r_fast_kernel, the plane bodies plane_fwd_body / plane_inv_body / plane_c2c_inv_body and their kernels' loads,
+    with n = n2, n2 / 2 + 1; the butterfly index of stage() with n = the stage stride and the line count).
     c stays below the real plane, 2 * PLANE_ENTRIES = 20480.  Evaluated here in IEEE single precision operation by operation,
     as the kernel does: equal to c // n for every n in 2..1024 (a change of the rounding, of the + 0.5f or of the plane limit
     that breaks this would scatter plane entries silently)."""
