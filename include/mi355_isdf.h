@@ -286,6 +286,18 @@ int isdf_block_apply(isdf_handle h, const double* d_Dinv, int64_t ldd, int nblk,
 int isdf_pair_rows_block_apply(isdf_handle h, const double* d_aoP, int P, int nao, const double* d_ao, int64_t ng,
                                int64_t ld, const double* d_Dinv, int64_t ldd, int nblk, const int32_t* blk_off,
                                double* d_B, int64_t ldb);
+/* The same with the product and the block apply on frontiers of their own, for a caller that produces the rows in pieces of
+ * full GEMM tiles while the blocks end where they end.  d_B is the caller's row scratch: its rows [0, have) were produced by
+ * earlier calls and not applied yet; rows [have, have + nnew) <- d_aoP (nnew, nao) d_ao; then the blocks of blk_off
+ * (blk_off[0] = 0, blk_off[nblk] <= have + nnew, nblk = 0: none; d_Dinv at the first block's diagonal sub-block) are
+ * overwritten with Dinv_b (.)^2.  Rows past blk_off[nblk] stay as produced.  squared != 0: the products carry the square
+ * (the own NN kernel's epilogue, option "gemm_nn_own"), 0: the block apply squares while staging - one answer per build, from
+ * isdf_pair_rows_squared for the build's piece size.  Element for element the result is isdf_pair_rows_block_apply's. */
+int isdf_pair_rows_squared(isdf_handle h, const double* d_aoP, int rows, int nao, const double* d_ao, int64_t ng,
+                           int64_t ld, int* squared);
+int isdf_pair_rows_frontier(isdf_handle h, const double* d_aoP, int nnew, int nao, const double* d_ao, int64_t ng,
+                            int64_t ld, int squared, const double* d_Dinv, int64_t ldd, int nblk, const int32_t* blk_off,
+                            double* d_B, int64_t ldb, int have);
 
 /* The (AO x occupied orbital) pair space: what the reference's K works on when the density matrix carries its orbitals
  * (mo_coeff / mo_occ tag, pyscf/pbc/df/fft_jk.py:206-210,235-238: pair densities phi_mu psi_i, N x N_occ of them instead of

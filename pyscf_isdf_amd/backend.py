@@ -348,6 +348,27 @@ class HipBackend:
         self.handle.call('isdf_pair_rows_block_apply', self._p(aoP), aoP.shape[0], aoP.shape[1], self._p(ao), int(ng), ao.stride(0),
                          self._p(Dinv), Dinv.stride(0), len(blk_off) - 1, _np_ptr(blk_off), self._p(B), B.stride(0))
 
+    def pair_rows_squared(self, aoP, rows, ao, ng):
+        """Whether pair_rows_frontier's products of ``rows`` rows carry the square themselves (asked once per build)."""
+        self._stream()
+        sq = ctypes.c_int(0)
+        self.handle.call('isdf_pair_rows_squared', self._p(aoP), int(rows), aoP.shape[1], self._p(ao), int(ng), ao.stride(0),
+                         ctypes.byref(sq))
+        return bool(sq.value)
+
+    def pair_rows_frontier(self, aoP_new, ao, ng, squared, Dinv, blk_off, B, have):
+        """B[have:have + len(aoP_new)] <- aoP_new ao, then the blocks blk_off (rows of B from 0; may end before the produced
+        rows, or be [0]: none) <- Dinv_b (.)^2; Dinv: the diagonal sub-block view starting at the first of those blocks."""
+        self._stream()
+        blk_off = np.ascontiguousarray(blk_off, dtype=np.int32)
+        nnew = aoP_new.shape[0]
+        assert aoP_new.stride(1) == 1 and aoP_new.stride(0) == aoP_new.shape[1] and B.stride(1) == 1
+        assert have + nnew <= B.shape[0] and blk_off[0] == 0 and blk_off[-1] <= have + nnew and B.shape[1] >= ng
+        assert len(blk_off) == 1 or (Dinv.shape[0] >= blk_off[-1] and Dinv.shape[1] >= blk_off[-1])
+        self.handle.call('isdf_pair_rows_frontier', self._p(aoP_new) if nnew else None, nnew, aoP_new.shape[1], self._p(ao), int(ng),
+                         ao.stride(0), int(bool(squared)), self._p(Dinv) if len(blk_off) > 1 else None, Dinv.stride(0) if len(blk_off) > 1 else 0,
+                         len(blk_off) - 1, _np_ptr(blk_off), self._p(B), B.stride(0), int(have))
+
     def shift_diag(self, A, shift_rel):
         self._stream()
         self.handle.call('isdf_shift_diag', self._p(A), A.shape[0], float(shift_rel))

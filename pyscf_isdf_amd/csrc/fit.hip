@@ -469,6 +469,36 @@ extern "C" int isdf_pair_rows_block_apply(isdf_handle h, const double* d_aoP, in
   return block_apply_inverse(h, d_Dinv, ldd, nblk, blk_off, d_B, ldb, ng, !own);
 }
 
+extern "C" int isdf_pair_rows_squared(isdf_handle h, const double* d_aoP, int rows, int nao, const double* d_ao, int64_t ng,
+                                      int64_t ld, int* squared) {
+  // which of the two forms isdf_pair_rows_frontier's products take for pieces of `rows` rows: asked once per build
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_aoP && d_ao && squared && rows > 0 && nao > 0 && ng > 0 && ld >= ng);
+  *squared = gemm_nn_f64_supported(h, rows, ng, nao, d_aoP, nao, d_ao, ld) ? 1 : 0;
+  return ISDF_OK;
+}
+
+extern "C" int isdf_pair_rows_frontier(isdf_handle h, const double* d_aoP, int nnew, int nao, const double* d_ao, int64_t ng,
+                                       int64_t ld, int squared, const double* d_Dinv, int64_t ldd, int nblk,
+                                       const int32_t* blk_off, double* d_B, int64_t ldb, int have) {
+  // isdf_pair_rows_block_apply with the product and the block apply on frontiers of their own: the product's row count is the
+  // caller's (full GEMM tiles), the block boundaries bind the apply alone.  Rows [have, have + nnew) of B <- aoP ao, then
+  // the blocks of blk_off (rows [0, blk_off[nblk]) of B, all of them produced) <- Dinv_b (.)^2.  squared: the products of this
+  // build carry the square already (the own NN kernel's epilogue; a piece it does not take gets a pass of its own), else the
+  // block apply squares while staging.  Rows past blk_off[nblk] stay as produced for a later call.
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_ao && d_B && nnew >= 0 && nnew <= 65535 && have >= 0 && nblk >= 0 && nao > 0 && ng > 0 && ld >= ng && ldb >= ng);
+  ARG_CHECK(h, (nnew == 0 || d_aoP) && (nblk == 0 || (d_Dinv && blk_off && blk_off[0] == 0 && blk_off[nblk] <= have + nnew)));
+  if (nnew > 0) {
+    double* rows = d_B + (int64_t)have * ldb;
+    int rc = squared ? product_rows(h, nnew, ng, nao, d_aoP, d_ao, ld, rows, ldb, true)
+                     : gemm_rm(h, 'N', 'N', nnew, ng, nao, 1.0, d_aoP, nao, d_ao, ld, 0.0, rows, ldb);
+    if (rc) return rc;
+  }
+  if (nblk == 0) return ISDF_OK;
+  return block_apply_inverse(h, d_Dinv, ldd, nblk, blk_off, d_B, ldb, ng, !squared);
+}
+
 extern "C" int isdf_shift_diag(isdf_handle h, double* d_A, int P, double shift_rel) {
   // A <- A + shift_rel * max(diag A) * I  (the fit's regularisation, applied before the block scaling of S3c so that
   // both fit routes solve the same regularised normal equations)

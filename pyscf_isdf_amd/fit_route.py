@@ -352,9 +352,13 @@ class FitRouteMixin:
         self._last_fft_batch = nbat
         ldx = plan['ldx']
         X = self._buffer('theta', (P, ldx))
+        piece = self._pair_rows_piece(big)
         scratch = self._buffer('rows_scratch', (nbat + big, G))
         self.w_spectral_fraction = plan['fraction']
         self._last_spectral_ldx = ldx
+        if piece:
+            self._spectral_rows_two_frontiers(X, scratch, piece, plan, probe)
+            return self._spectral_W_finish(X, W, nbat)
         nxt, fill, g0 = 0, 0, 0
         while nxt < P or fill > 0:
             while fill < nbat and nxt < P:
@@ -375,11 +379,65 @@ class FitRouteMixin:
                 scratch[:fill - take].copy_(scratch[take:fill].clone() if fill - take > take else scratch[take:fill])
             g0 += take
             fill -= take
+        self._spectral_W_finish(X, W, nbat)
+
+    def _spectral_W_finish(self, X, W, nbat):
+        """M' = X X^T (upper half, nbat-row strips) and the route's P x P finishing."""
+        be, st = self.backend, self._fit_state
+        P = W.shape[0]
         for b0 in range(0, P, nbat):
             b1 = min(P, b0 + nbat)
             be.gemm_nt(X[b0:b1], X[b0:], W[b0:b1, b0:], alpha=1.0)
         be.symmetrize_upper(W)
         self._bj_finish(st['Afac'], st['Dblk'], st['ip_off'], W)
+
+    def _pair_rows_piece(self, big):
+        """Rows per pair-row product of the spectral build in its two-frontier form: the FFT batch rounded DOWN to a multiple of
+        ``pair_rows_align`` (256: the library's 128-row tile and the own NN kernel's 256-row one), so that the row scratch
+        (batch + largest block) holds a piece next to an open block's head without growing and _resident_rows stands as it
+        is.  0: the block-bound pieces - the switch is off, the batch is smaller than one aligned piece, the backend has no
+        isdf_pair_rows_frontier, the pair space or the block apply is another one (big: the largest block; _block_inverse has
+        the bound)."""
+        align = int(getattr(self, 'pair_rows_align', 0) or 0)
+        if align <= 0 or not hasattr(self.backend, 'pair_rows_frontier') or getattr(self, '_psi', None) is not None \
+                or not self.block_apply_mfma or big > 1100:
+            return 0
+        return int(self.fft_batch or 512) // align * align
+
+    def _spectral_rows_two_frontiers(self, X, scratch, piece, plan, probe):
+        """The fit rows of _finish_W_spectral with two frontiers.  The PRODUCT frontier advances in pieces of `piece` rows (full
+        GEMM tiles whatever the block sizes; only a build's last piece is ragged), unsquared into the row scratch.  The APPLIED
+        frontier follows on block boundaries: the whole blocks inside the produced rows get the block apply (the square in its
+        staging), the probe's combination and the transform into X; the produced tail of the block still open (fewer rows than
+        the largest block) moves to the front of the scratch for the next round.  Element for element the rows are those of
+        the block-bound pieces: a product's k chain does not depend on its row count, the rest works per block and per row."""
+        be, st = self.backend, self._fit_state
+        ip_off = np.asarray(st['ip_off'], dtype=np.int64)
+        P = int(ip_off[-1])
+        mesh = np.asarray(self.mesh, dtype=np.int32)
+        G = self.ao.shape[1]
+        Dinv = self._block_inverse(st['Dblk'], ip_off)
+        nbat = int(self.fft_batch or 512)
+        squared = be.pair_rows_squared(self.aoP, min(piece, P), self.ao, G)      # one answer for the whole build
+        app, prod = 0, 0                                   # rows [0, app) are in X; scratch row 0 is row `app`
+        while app < P:
+            new = min(piece, P - prod)
+            j = int(np.searchsorted(ip_off, prod + new, side='right')) - 1       # last block boundary inside the produced rows
+            i = int(np.searchsorted(ip_off, app))
+            end = int(ip_off[j])
+            be.pair_rows_frontier(self.aoP[prod:prod + new], self.ao, G, squared, Dinv[app:, app:],
+                                  (ip_off[i:j + 1] - app).astype(np.int32), scratch, prod - app)
+            prod += new
+            if end > app:
+                rows = scratch[:end - app]
+                if probe is not None:
+                    be.rows_combine(probe[0][:, app:end], rows, probe[1], accumulate=app > 0)
+                be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[app:end], batch=min(nbat, end - app))
+                tail = prod - end
+                if tail > 0:
+                    src = scratch[end - app:prod - app]
+                    scratch[:tail].copy_(src.clone() if tail > end - app else src)
+                app = end
 
     def _bj_finish(self, Afac, Dblk, ip_off, W, antisymmetric=False):
         """W <- D^-T [A'^-1 W A'^-1] D^-1 (W holds M' on entry)."""

@@ -111,6 +111,9 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                                          # Theta itself and keeps V = conv(Theta) on the device; K costs 4 N G P flop
         self.explicit_theta = False      # True: form Theta itself (second O(P^2 G) solve); same W in exact arithmetic
         self.fft_batch = None             # rows per FFT batch (None: sized from free memory)
+        self.pair_rows_align = 256        # spectral W: the pair-row products come in pieces of the FFT batch rounded down to a multiple of
+                                          # this (full GEMM tiles) while the block apply follows on block boundaries; 0, or a batch below
+                                          # it: pieces of whole blocks.  Same X and W to the bit; the probe sums its rows in other groups
         self.block_apply_mfma = True      # block solves over the grid through explicit block inverses on the matrix cores
         self.max_resident_rows = None     # fit rows held in HBM at once (None: from free memory); fewer than the number of
                                           # points -> the rows are produced panel by panel (block-Jacobi route)

@@ -58,6 +58,9 @@ SIGNATURES = {
     'isdf_block_invert': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'isdf_block_apply': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_i64]),
     'isdf_pair_rows_block_apply': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_i64]),
+    'isdf_pair_rows_squared': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_i64, ctypes.POINTER(c_int)]),
+    'isdf_pair_rows_frontier': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_i64,
+                                        c_int]),
     'isdf_shift_diag': (c_int, [c_vp, c_vp, c_int, c_dbl]),
     'isdf_chol_inplace': (c_int, [c_vp, c_vp, c_int, c_dbl, c_vp, ctypes.POINTER(c_dbl)]),
     'isdf_factor_solve': (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_i64]),
