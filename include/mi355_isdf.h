@@ -624,6 +624,18 @@ int isdf_gemm_nt(isdf_handle h, int M, int N, int64_t K, double alpha, const dou
                  const double* d_B, int64_t ldb, const double* d_kscale, double beta, double* d_C,
                  int64_t ldc);
 
+/* Three-component Hadamard NT product, the hot loop of the half-fitted exchange derivative:
+ *   C_a (M, ldc) = beta C_a + alpha sum_k A[m,k] H[m,k] B_a[n,k],   a = 0, 1, 2,   B_a = d_B + a bstride, C_a = d_C + a cstride,
+ * K contiguous in A (M, lda), H (M, ldh) and B_a (N, ldb); d_H may be NULL (no Hadamard factor).  A is not modified.
+ * ONE launch for the three components: variant D of the NT kernel with the factor multiplied into the A operand registers (A o H
+ * is never stored) and a 128 x 32 tile of all three components per unit; deterministic slab reduction.  That kernel takes
+ * K % 16 == 0, even lda / ldh / ldb / bstride and 16-byte aligned A, H, B; every other alignment runs the composition inside
+ * this entry point (a copy of A times H in the workspace, then three isdf_gemm_nt).  The C_a must not overlap
+ * (cstride >= (M - 1) ldc + N); bstride >= 0. */
+int isdf_gemm_nt_had3(isdf_handle h, int M, int N, int64_t K, double alpha, const double* d_A, int64_t lda, const double* d_H,
+                      int64_t ldh, const double* d_B, int64_t ldb, int64_t bstride, double beta, double* d_C, int64_t ldc,
+                      int64_t cstride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -534,6 +534,18 @@ class HipBackend:
         self.handle.call('isdf_gemm_nt', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(B), B.stride(0), ks,
                          float(beta), self._p(C), C.stride(0))
 
+    def gemm_nt_had3(self, A, H, B3, C3, alpha=1.0, beta=0.0):
+        """C3[a] = beta C3[a] + alpha (A .* H) B3[a]^T for a = 0, 1, 2 in one launch; A, H (M, K), B3 (3, N, K), C3 (3, M, N), K and N
+        contiguous; H may be None (include/mi355_isdf.h isdf_gemm_nt_had3)."""
+        self._stream()
+        M, K = A.shape
+        N = B3.shape[1]
+        assert tuple(B3.shape) == (3, N, K) and tuple(C3.shape) == (3, M, N) and A.stride(1) == 1 and B3.stride(2) == 1 and C3.stride(2) == 1
+        assert H is None or (tuple(H.shape) == (M, K) and H.stride(1) == 1)
+        self.handle.call('isdf_gemm_nt_had3', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(H) if H is not None else _vp(0),
+                         H.stride(0) if H is not None else 0, self._p(B3), B3.stride(1), B3.stride(0), float(beta), self._p(C3),
+                         C3.stride(1), C3.stride(0))
+
     # ---- k-point M^q from the packed half spectra of the fit rows (DESIGN.md section 6b) ------------------------------------
     def pack_table_pm(self, table, mesh, idx, scale, s, a):
         """s, a (ldx,) <- scale (c(G_t) +- (m_t - 1) c(-G_t)) on the packed points idx (int32 half-spectrum indices), each value on

@@ -23,6 +23,8 @@
 //        64 -> 69 TF/s, and it keeps co-scheduled workgroups in step so that shared operand panels hit in L2 (fabric
 //        traffic 3.9x -> 1.3x the algorithmic bytes).
 //    Algorithmic work: 2*M*N*K flop; bound: FP64 MFMA (78.6 TF/s).
+//  * gemm_nt_had3: C_a += alpha (A o H) B_a^T for three B_a in one launch (the exchange derivative's T_a): variant D with the
+//    factor H multiplied into the A operand registers and a 128 x 32 tile of all three components per unit.
 //  * Every kernel finds its unit with xcd_unit / decode_tile / slab_range (the NN form: decode_supertile) and stores its
 //    accumulators with ISDF_STORE_ACC.  Variant B's unit body, tile_256x128, is a function template that leaves the tile in
 //    accumulator registers: gemm_nt_mfma_kernel_b and the Gram triangles are that body between two ways of finding a unit
@@ -540,6 +542,189 @@ __global__ __launch_bounds__(TPBD, 2) void gemm_nt_mfma_kernel_d(GemmArgs g) {
 #undef ISDF_CHUNKD
 }
 
+// ---- three-component Hadamard NT product: T_a = sum_g (F o V)(P, g) dphi_a(mu, g) of the exchange derivative
+//   C_a = beta C_a + alpha sum_k A[m,k] H[m,k] B_a[n,k],  a = 0, 1, 2,  B_a = B + a bstride, C_a = C + a cstride.
+// Variant D's operand scheme: a lane loads its four consecutive k of an A row straight into MFMA operand registers, so the
+// factor H costs one more load of the same shape and one multiply per element, and A o H exists only in registers.  Three
+// 128 x 128 accumulator sets (384 VGPRs) do not fit the 256 registers of two waves per SIMD, so the N tile is narrowed: one
+// unit is 128 rows x 32 columns of ALL three components (four waves stacked along M, 32 rows x 32 columns x 3 each = 12
+// accumulators, 96 VGPRs), and A o H is formed once for the three.  The staged B tile is 3 x 32 rows x 16: component a of
+// thread tid is row tid / 8, k offset 2 (tid % 8) - one double2 per component.  Register sets X / Y alternate between chunks
+// as in variant D (every load has a chunk of MFMAs to land); an odd chunk count ends with one more chunk after the paired
+// loop (a break in the middle of the loop body cost 152 - 312 bytes of scratch), so K only has to be a multiple of 16.  Units,
+// XCD remap, slabs and their fixed-order reduction are those of the NT kernels; the partials are [slab][component][M][N].
+// 208 VGPRs with H, 176 without, no scratch (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage).
+constexpr int BN3 = 32;
+
+struct Had3Args {
+  const double* A; int64_t lda;
+  const double* H; int64_t ldh;  // nullptr: no Hadamard factor
+  const double* B; int64_t ldb, bstride;
+  double* P;                     // partials [nslab][3][M][N] (or C itself when direct)
+  int64_t ldp, pstride, slab_stride;
+  int M, N;
+  int64_t K, kslab;              // kslab multiple of BK
+  int ntm, ntn, nslab;
+  int64_t nunits, nunits_pad;
+  double alpha, beta;            // used only when direct
+  int direct;
+};
+
+template <bool HAD>
+__global__ __launch_bounds__(TPBD, 2) void gemm_nt_had3_kernel(Had3Args g) {
+  __shared__ double sB[2][3 * BN3 * LDT];
+  const int64_t unit = xcd_unit(g.nunits_pad);
+  if (unit >= g.nunits) return;
+  const Tile t = decode_tile(unit, g.ntm, g.ntn);
+  const int tm = t.tm, tn = t.tn;
+  const KRange kr = slab_range(t.slab, g.kslab, g.K);
+  const int64_t k0 = kr.k0;
+  const int nchunks = (int)((kr.k1 - k0) / BK);         // any count >= 1 (K % 16 == 0, kslab a multiple of 16)
+  const int last = nchunks - 1;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int frow = lane & 15, fkq = lane >> 4;
+  const int mlast = g.M - 1, nlast = g.N - 1;
+  // A and H: two 16-row groups of this wave's 32 rows, four consecutive k per lane; rows past the edge are clamped
+  const int ar0 = min(tm * BM + wave * 32 + frow, mlast), ar1 = min(tm * BM + wave * 32 + 16 + frow, mlast);
+  const double* pA0 = g.A + (int64_t)ar0 * g.lda + k0 + 4 * fkq;
+  const double* pA1 = g.A + (int64_t)ar1 * g.lda + k0 + 4 * fkq;
+  const double* pH0 = HAD ? g.H + (int64_t)ar0 * g.ldh + k0 + 4 * fkq : nullptr;
+  const double* pH1 = HAD ? g.H + (int64_t)ar1 * g.ldh + k0 + 4 * fkq : nullptr;
+  // B staging: row srow of each component's 32-row tile, k offset 2 sseg
+  const int srow = tid >> 3, sseg = tid & 7;
+  const double* pB0 = g.B + (int64_t)min(tn * BN3 + srow, nlast) * g.ldb + k0 + 2 * sseg;
+  const double* pB1 = pB0 + g.bstride;
+  const double* pB2 = pB1 + g.bstride;
+
+  double2 xa00, xa01, xa10, xa11, xh00, xh01, xh10, xh11, xb0, xb1, xb2;
+  double2 ya00, ya01, ya10, ya11, yh00, yh01, yh10, yh11, yb0, yb1, yb2;
+#define ISDF_LOAD3(C, A00, A01, A10, A11, H00, H01, H10, H11, B0, B1, B2)                     \
+  {                                                                                           \
+    const int off = (C) * BK;                                                                 \
+    A00 = *reinterpret_cast<const double2*>(pA0 + off);                                       \
+    A01 = *reinterpret_cast<const double2*>(pA0 + off + 2);                                   \
+    A10 = *reinterpret_cast<const double2*>(pA1 + off);                                       \
+    A11 = *reinterpret_cast<const double2*>(pA1 + off + 2);                                   \
+    if (HAD) {                                                                                \
+      H00 = *reinterpret_cast<const double2*>(pH0 + off);                                     \
+      H01 = *reinterpret_cast<const double2*>(pH0 + off + 2);                                 \
+      H10 = *reinterpret_cast<const double2*>(pH1 + off);                                     \
+      H11 = *reinterpret_cast<const double2*>(pH1 + off + 2);                                 \
+    }                                                                                         \
+    B0 = *reinterpret_cast<const double2*>(pB0 + off);                                        \
+    B1 = *reinterpret_cast<const double2*>(pB1 + off);                                        \
+    B2 = *reinterpret_cast<const double2*>(pB2 + off);                                        \
+  }
+  // A <- A o H, in the operand registers
+#define ISDF_MUL3(A00, A01, A10, A11, H00, H01, H10, H11)                                     \
+  if (HAD) {                                                                                  \
+    A00.x *= H00.x; A00.y *= H00.y; A01.x *= H01.x; A01.y *= H01.y;                           \
+    A10.x *= H10.x; A10.y *= H10.y; A11.x *= H11.x; A11.y *= H11.y;                           \
+  }
+#define ISDF_STORE3(BUF, B0, B1, B2)                                                          \
+  {                                                                                           \
+    double* q = &sB[BUF][srow * LDT + 2 * sseg];                                              \
+    q[0] = B0.x; q[1] = B0.y;                                                                 \
+    q[BN3 * LDT] = B1.x; q[BN3 * LDT + 1] = B1.y;                                             \
+    q[2 * BN3 * LDT] = B2.x; q[2 * BN3 * LDT + 1] = B2.y;                                     \
+  }
+
+  d4 acc[6][2];                                         // [2 a + jn][i]: component a, column group jn, row group i
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) acc[q][i] = (d4){0.0, 0.0, 0.0, 0.0};
+
+  // fragments: element j of a lane's four k is k = 4 fkq + j (variant D's map); the six 16-row groups of the staged tile
+  // (component-major) are 16 LDT apart
+  double bf0[6], bf1[6];
+#define ISDF_FRAG3(BUF, J, BF)                                                                \
+  {                                                                                           \
+    const double* pb = &sB[BUF][frow * LDT + 4 * fkq + (J)];                                  \
+    _Pragma("unroll") for (int q = 0; q < 6; ++q) BF[q] = pb[q * 16 * LDT];                   \
+  }
+#define ISDF_MFMA3(AV0, AV1, BF)                                                              \
+    _Pragma("unroll") for (int q = 0; q < 6; ++q) {                                           \
+      acc[q][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(AV0, BF[q], acc[q][0], 0, 0, 0);       \
+      acc[q][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(AV1, BF[q], acc[q][1], 0, 0, 0);       \
+    }
+  // one chunk, variant D's order: the fragments of the NEXT k-step are read from LDS under the MFMAs of the current one (one
+  // read after every second MFMA: six rounds for the twelve MFMAs of a k-step), the next chunk's B part goes to the other buffer
+  // during k-step 2, the chunk's single barrier sits after k-step 2, and k-step 3 already prefetches the first fragments of the
+  // next chunk from the other buffer while the loads of the chunk after next are issued
+#define ISDF_ISSUE3(XMASK, NX) _Pragma("unroll") for (int q_ = 0; q_ < 6; ++q_) {             \
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                \
+    if (q_ < (NX)) __builtin_amdgcn_sched_group_barrier(XMASK, 1, 0); }
+#define ISDF_CHUNK3(BUF, A00, A01, A10, A11, LOAD_AHEAD, STORE_NEXT)                          \
+  {                                                                                           \
+    ISDF_FRAG3(BUF, 1, bf1)                                                                   \
+    ISDF_MFMA3(A00.x, A10.x, bf0)                                                             \
+    ISDF_ISSUE3(0, 0)                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    ISDF_FRAG3(BUF, 2, bf0)                                                                   \
+    ISDF_MFMA3(A00.y, A10.y, bf1)                                                             \
+    ISDF_ISSUE3(0, 0)                                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    ISDF_FRAG3(BUF, 3, bf1)                                                                   \
+    STORE_NEXT                                                                                \
+    ISDF_MFMA3(A01.x, A11.x, bf0)                                                             \
+    ISDF_ISSUE3(0x200, 6)                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    __syncthreads();                                                                          \
+    ISDF_FRAG3(1 - (BUF), 0, bf0)                                                             \
+    ISDF_MFMA3(A01.y, A11.y, bf1)                                                             \
+    LOAD_AHEAD                                                                                \
+    ISDF_ISSUE3(0x020, 6)                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+  }
+
+  // prologue: chunk 0 in set X (its B part published in buffer 0), chunk 1 in flight in set Y, first fragments of chunk 0
+  ISDF_LOAD3(0, xa00, xa01, xa10, xa11, xh00, xh01, xh10, xh11, xb0, xb1, xb2)
+  ISDF_LOAD3(min(1, last), ya00, ya01, ya10, ya11, yh00, yh01, yh10, yh11, yb0, yb1, yb2)
+  ISDF_STORE3(0, xb0, xb1, xb2)
+  __syncthreads();
+  ISDF_FRAG3(0, 0, bf0)
+  __builtin_amdgcn_sched_barrier(0);
+  for (int c = 0; c + 1 < nchunks; c += 2) {
+    // chunk c: A o H from set X, B in buffer 0; chunk c + 1 sits in Y (its B part goes to buffer 1 during k-step 2); X is
+    // refilled with chunk c + 2 once its last use (k-step 3) has been issued
+    ISDF_MUL3(xa00, xa01, xa10, xa11, xh00, xh01, xh10, xh11)
+    ISDF_CHUNK3(0, xa00, xa01, xa10, xa11,
+                ISDF_LOAD3(min(c + 2, last), xa00, xa01, xa10, xa11, xh00, xh01, xh10, xh11, xb0, xb1, xb2),
+                ISDF_STORE3(1, yb0, yb1, yb2))
+    ISDF_MUL3(ya00, ya01, ya10, ya11, yh00, yh01, yh10, yh11)
+    ISDF_CHUNK3(1, ya00, ya01, ya10, ya11,
+                ISDF_LOAD3(min(c + 3, last), ya00, ya01, ya10, ya11, yh00, yh01, yh10, yh11, yb0, yb1, yb2),
+                ISDF_STORE3(0, xb0, xb1, xb2))
+  }
+  if (nchunks & 1) {
+    // an odd count: the last chunk sits in set X with its B part in buffer 0 and its first fragments in bf0 (from the prologue
+    // or the last pair); what its k-step 3 prefetches from buffer 1 is not used
+    ISDF_MUL3(xa00, xa01, xa10, xa11, xh00, xh01, xh10, xh11)
+    ISDF_CHUNK3(0, xa00, xa01, xa10, xa11, , )
+  }
+  // the unit's three tiles: the slab's partials, or C itself (direct) with alpha and beta
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double* out = g.P + (int64_t)t.slab * g.slab_stride + (int64_t)a * g.pstride;
+    ISDF_STORE_ACC(2, 2, tm * BM + wave * 32, tn * BN3, g.M, g.N, {
+      double* q = out + (int64_t)row * g.ldp + col;
+      const double v = acc[2 * a + j][i][r];
+      if (g.direct) *q = (g.beta == 0.0) ? g.alpha * v : g.alpha * v + g.beta * (*q);
+      else *q = v;
+    })
+  }
+#undef ISDF_LOAD3
+#undef ISDF_MUL3
+#undef ISDF_STORE3
+#undef ISDF_FRAG3
+#undef ISDF_MFMA3
+#undef ISDF_ISSUE3
+#undef ISDF_CHUNK3
+}
+
 // ---- NN form: C = A B (optionally squared element-wise), A (M x K) with K contiguous, B (K x N) with N contiguous, K short
 // (the AO count) and N long (the grid): the pair-density rows (phi_P^T phi)^2 of the fit.  Same 256x128 tile, 8 waves, register
 // double buffering and pinned issue order as variant B; what changes is the B operand: a chunk is 16 full 1-KB rows of the
@@ -993,6 +1178,68 @@ extern "C" int isdf_gemm_nt(isdf_handle h, int M, int N, int64_t K, double alpha
                             double beta, double* d_C, int64_t ldc) {
   if (!h) return ISDF_ERR_ARG;
   return gemm_nt_f64_scaled(h, M, N, K, alpha, d_A, lda, d_B, ldb, d_kscale, beta, d_C, ldc);
+}
+
+// Exposed as isdf_gemm_nt_had3 (declared in include/mi355_isdf.h).
+extern "C" int isdf_gemm_nt_had3(isdf_handle h, int M, int N, int64_t K, double alpha, const double* d_A, int64_t lda,
+                                 const double* d_H, int64_t ldh, const double* d_B, int64_t ldb, int64_t bstride, double beta,
+                                 double* d_C, int64_t ldc, int64_t cstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, M > 0 && N > 0 && K > 0 && d_A && d_B && d_C && lda >= K && (!d_H || ldh >= K) && ldb >= K && ldc >= N);
+  ARG_CHECK(h, bstride >= 0 && cstride >= (int64_t)(M - 1) * ldc + N);
+  const bool fused = K % BK == 0 && rows_aligned16(d_A, lda) && (!d_H || rows_aligned16(d_H, ldh)) && rows_aligned16(d_B, ldb) &&
+                     bstride % 2 == 0;
+  if (!fused) {
+    // other alignments: the composition - a copy of A times H, then one NT product per component
+    const double* A = d_A;
+    int64_t la = lda;
+    if (d_H) {
+      double* AH = (double*)isdf_ws(h, "had3_AH", sizeof(double) * (size_t)M * (size_t)K);
+      if (!AH) return ISDF_ERR_HIP;
+      HIP_TRY(h, hipMemcpy2DAsync(AH, sizeof(double) * (size_t)K, d_A, sizeof(double) * (size_t)lda, sizeof(double) * (size_t)K,
+                                  (size_t)M, hipMemcpyDeviceToDevice, h->stream));
+      for (int r0 = 0; r0 < M; r0 += 32768) {
+        const int nr = M - r0 < 32768 ? M - r0 : 32768;
+        if (int rc = isdf_hadamard_rows(h, AH + (int64_t)r0 * K, K, d_H + (int64_t)r0 * ldh, ldh, nr, K)) return rc;
+      }
+      A = AH; la = K;
+    }
+    for (int a = 0; a < 3; ++a)
+      if (int rc = gemm_nt_f64(h, M, N, K, alpha, A, la, d_B + a * bstride, ldb, beta, d_C + a * cstride, ldc)) return rc;
+    return ISDF_OK;
+  }
+  Had3Args g;
+  g.A = d_A; g.lda = lda; g.H = d_H; g.ldh = ldh; g.B = d_B; g.ldb = ldb; g.bstride = bstride;
+  g.M = M; g.N = N; g.K = K;
+  g.ntm = (int)cdiv(M, BM); g.ntn = (int)cdiv(N, BN3);
+  // two workgroups per CU; three components per entry of the M x N output share the 2 GiB of partials
+  const SlabPlan p = plan_slabs((int64_t)g.ntm * g.ntn, (int64_t)h->num_cu * 2, M, N, K, 24, BK, true);
+  g.kslab = p.kslab; g.nslab = p.nslab; g.nunits = p.nunits; g.nunits_pad = p.nunits_pad;
+  ARG_CHECK(h, g.nunits_pad < 2147483647LL);
+  g.alpha = alpha; g.beta = beta;
+  const int64_t plane = (int64_t)M * N;
+  if (g.nslab == 1) {
+    g.direct = 1; g.P = d_C; g.ldp = ldc; g.pstride = cstride; g.slab_stride = 0;
+  } else {
+    g.direct = 0;
+    g.P = (double*)isdf_ws(h, "gemm_partials", sizeof(double) * (size_t)g.nslab * 3 * plane);
+    if (!g.P) return ISDF_ERR_HIP;
+    g.ldp = N; g.pstride = plane; g.slab_stride = 3 * plane;
+  }
+  {
+    ProfScope ps(h, d_H ? "gemm_nt_had3_kernel<true>[flop]" : "gemm_nt_had3_kernel<false>[flop]", 6.0 * M * N * (double)K);
+    if (d_H) hipLaunchKernelGGL(gemm_nt_had3_kernel<true>, dim3((unsigned)g.nunits_pad), dim3(TPBD), 0, h->stream, g);
+    else hipLaunchKernelGGL(gemm_nt_had3_kernel<false>, dim3((unsigned)g.nunits_pad), dim3(TPBD), 0, h->stream, g);
+    KERNEL_CHECK(h);
+  }
+  if (!g.direct) {
+    ProfScope ps(h, "gemm_reduce_slabs_kernel[byte]", 24.0 * (double)plane * (g.nslab + 1));
+    for (int a = 0; a < 3; ++a)
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)cdiv(plane, 256)), dim3(256), 0, h->stream, g.P + a * plane, g.nslab,
+                         g.slab_stride, M, N, alpha, beta, d_C + a * cstride, ldc);
+    KERNEL_CHECK(h);
+  }
+  return ISDF_OK;
 }
 
 int gram_tri_blocks(isdf_handle h, const double* X, int64_t ldx, int K, const GramTriUnit* d_units, int64_t nunits,

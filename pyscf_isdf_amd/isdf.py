@@ -12,7 +12,7 @@ What runs where: this file and its mixins are host orchestration only (which sta
 every stage executes in libmi355_isdf.so via ``backend.HipBackend``.  There is no CPU path.
 Modules: ``isdf`` (the object, Gamma-point single-GPU build and get_jk, ERIs, range separation), ``fit_route`` (fit routes and
 the probe check), ``sharded`` (grid-sharded multi-GPU build), ``kpoints`` (k-points, band k-points, k-point ERIs),
-``hcore`` (get_nuc / get_pp).
+``hcore`` (get_nuc / get_pp), ``jk_e1`` (get_j_e1 / get_k_e1 / get_jk_e1, the derivative matrices of pbc.grad).
 """
 import os
 import sys
@@ -28,9 +28,10 @@ from .sharded import ShardedMixin
 from .kpoints import KPointMixin
 from .hcore import HcoreMixin
 from .eri_surface import EriSurfaceMixin
+from .jk_e1 import JKE1Mixin
 
 
-class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin):
+class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin, JKE1Mixin):
     _keys = {'cell', 'kpts', 'grids', 'mesh', 'blockdim', 'exxdiv', 'c_isdf', 'select', 'tie_rtol'}
 
     def __init__(self, cell, kpts=np.zeros((1, 3)), c_isdf=12, select='refined', backend=None, comm=None):
@@ -796,6 +797,10 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
 
             def get_jk(self, dm, hermi=1, kpts=None, kpts_band=None, with_j=True, with_k=True, omega=None, exxdiv=None):
                 return parent.get_jk(dm, hermi, kpts, kpts_band, with_j, with_k, omega if omega is not None else omega_, exxdiv)
+
+            def get_jk_e1(self, *args, **kwargs):
+                return parent._e1_refuse_omega()
+            get_j_e1 = get_k_e1 = get_jk_e1
         omega_ = omega
 
         @contextlib.contextmanager
