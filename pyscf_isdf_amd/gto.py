@@ -103,7 +103,12 @@ def load_pseudo(name, symb):
     if key not in ('gthpade', 'gthlda'):
         raise KeyError('pseudopotential %r is not bundled (bundled: gth-pade)' % name)
     with open(os.path.join(_BASIS_DIR, 'gth_pade_pp.dat')) as f:
-        lines = [ln.split('#')[0].strip() for ln in f.read().splitlines()]
+        return parse_pseudo(f.read(), symb)
+
+
+def parse_pseudo(text, symb):
+    """The first GTH-PADE entry of element ``symb`` in CP2K-format ``text``, in the layout of ``load_pseudo``."""
+    lines = [ln.split('#')[0].strip() for ln in text.splitlines()]
     lines = [ln for ln in lines if ln]
     for i, ln in enumerate(lines):
         tok = ln.split()
@@ -111,7 +116,7 @@ def load_pseudo(name, symb):
             it = iter(lines[i + 1:])
             break
     else:
-        raise KeyError('no bundled GTH-PADE pseudopotential for %s' % symb)
+        raise KeyError('no GTH-PADE pseudopotential for %s' % symb)
     nelec = [int(x) for x in next(it).split()]
     row = next(it).split()
     rloc, nexp = float(row[0]), int(row[1])
