@@ -515,6 +515,33 @@ int isdf_pp_projector_overlaps(isdf_handle h, const int32_t* atm, int natm, cons
                                const int32_t* proj_tab, const double* proj_rl, int nproj,
                                const int32_t mesh[3], const double a[9], double* d_out);
 
+/* ---- nuclear derivative of tr(D get_pp) and of any local potential's energy (the pseudopotential part of
+ * pyscf/pbc/grad/krhf.py:86-209 without its N^2 G pair array) ----------------------------------------------------------
+ * isdf_pp_local_force:  d_out (nset, natm, 3) = the Hellmann-Feynman force of the local part,
+ *       HF[s, a, x] = sum_g rho_s(g) Re ifft(i G_x SI_a vloc_a)(g) = 1/G Re sum_G i G_x SI_a(G) vloc_a(G) conj(fft(rho_s)(G)),
+ *     by Parseval: one forward transform per density row d_rho (nset, ldrho) (device, real, not modified), then a sum over the
+ *     full spectrum - no transform per atom.  G of the unpaired -n/2 index of an even axis as in isdf_pp_local_potential, whose
+ *     vloc_a(G) this shares; coords / pp_par as there (host).  A workgroup takes 4 atoms x 2 density rows x 2048 G with its
+ *     accumulators in registers; a second launch sums the workgroups' partials in a fixed order: no atomics, repeatable bits.
+ * isdf_pp_projector_overlaps_ip:  d_out (4, nrows, nao) complex; component 0 is isdf_pp_projector_overlaps, component 1 + x is
+ *       sum_G (i G_x) conj(SI_a(G)) p_j(G+k) aoG_mu(G+k)
+ *     from the same pass (one zgemm of 4 nrows rows per chunk).  The weight is the lattice vector G, not G + k: it is the
+ *     derivative with respect to the projector's atom R_a.  At Gamma the overlap depends on R_a - R_mu only, so the same number is
+ *     minus the derivative with respect to the AO's atom, i.e. the overlap of the projector with grad phi_mu; away from Gamma only
+ *     the projector-side derivative is what comes out.
+ * isdf_rowdot3:  d_out[x * ldo + m] (+)= alpha sum_k A_x[m, k] s[k] B[m, k], x = 0, 1, 2, A_x = d_A + x astride (M, lda), B (M, ldb),
+ *     K contiguous; accumulate = 0 overwrites.  The contraction of a local potential's Pulay force: A_x the three grad phi planes
+ *     of isdf_eval_ao_deriv1, s the potential, B = D phi.  One workgroup per row, 16-byte loads when every base is 16-byte
+ *     aligned and lda, ldb, astride are even, scalar loads otherwise; fixed summation order. */
+int isdf_pp_local_force(isdf_handle h, const double* d_rho, int nset, int64_t ldrho, int natm, const double* coords,
+                        const double* pp_par, const int32_t mesh[3], const double a[9], double* d_out);
+int isdf_pp_projector_overlaps_ip(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas,
+                                  const double* env, int nenv, const double* coords, const double kpt[3],
+                                  const int32_t* proj_tab, const double* proj_rl, int nproj,
+                                  const int32_t mesh[3], const double a[9], double* d_out);
+int isdf_rowdot3(isdf_handle h, int M, int64_t K, double alpha, const double* d_A, int64_t lda, int64_t astride, const double* d_s,
+                 const double* d_B, int64_t ldb, int accumulate, double* d_out, int64_t ldo);
+
 /* Robust-fitting K (Dunlap's correction on top of the ISDF exchange).  With V_P = conv(Theta_P) kept
  * on the device, per batch of points:  F (nb, G) = (phi_P D)(nb, N) . phi (N, G)  [isdf_gemm_nn],  F .*= V rows
  * [isdf_hadamard_rows],  (F phi^T)(nb, N) [isdf_gemm_nt]  ->  K1 = w phi_P^T (F phi^T);  K = K1 + K1^T - K_isdf.

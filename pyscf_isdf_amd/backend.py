@@ -820,6 +820,36 @@ class HipBackend:
                          self._p(vlocR))
 
     def pp_projector_overlaps(self, atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out):
+        self._pp_overlaps('isdf_pp_projector_overlaps', atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out)
+
+    def pp_projector_overlaps_ip(self, atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out):
+        """out (4, nrows, nao) complex: the overlaps and their three i G_x weighted forms (include/mi355_isdf.h)."""
+        assert out.dim() == 3 and out.shape[0] == 4
+        self._pp_overlaps('isdf_pp_projector_overlaps_ip', atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out)
+
+    def pp_local_force(self, rho, coords, pp_par, mesh, a, out):
+        """out (nset, natm, 3) <- the local Hellmann-Feynman force of the real density rows rho (nset, G)."""
+        self._stream()
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        pp_par = np.ascontiguousarray(pp_par, dtype=np.float64)
+        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        nset = rho.shape[0]
+        assert rho.dim() == 2 and rho.stride(1) == 1 and rho.shape[1] == int(np.prod(mesh))
+        assert out.is_contiguous() and tuple(out.shape) == (nset, len(coords), 3) and tuple(pp_par.shape) == (len(coords), 8)
+        self.handle.call('isdf_pp_local_force', self._p(rho), nset, rho.stride(0), len(coords), _np_ptr(coords), _np_ptr(pp_par),
+                         _np_ptr(mesh), _np_ptr(a), self._p(out))
+
+    def rowdot3(self, A3, s, B, out, alpha=1.0, accumulate=False):
+        """out[x, m] (+)= alpha sum_k A3[x, m, k] s[k] B[m, k]; A3 (3, M, K), B (M, K), s (K,), out (3, M), K contiguous."""
+        self._stream()
+        M, K = B.shape
+        assert tuple(A3.shape) == (3, M, K) and A3.stride(2) == 1 and B.stride(1) == 1 and s.numel() == K and s.stride(0) == 1
+        assert tuple(out.shape) == (3, M) and out.stride(1) == 1
+        self.handle.call('isdf_rowdot3', M, K, float(alpha), self._p(A3), A3.stride(1), A3.stride(0), self._p(s), self._p(B),
+                         B.stride(0), int(bool(accumulate)), self._p(out), out.stride(0))
+
+    def _pp_overlaps(self, entry, atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out):
         self._stream()
         atm = np.ascontiguousarray(atm, dtype=np.int32)
         bas = np.ascontiguousarray(bas, dtype=np.int32)
@@ -831,6 +861,6 @@ class HipBackend:
         mesh = np.ascontiguousarray(mesh, dtype=np.int32)
         a = np.ascontiguousarray(a, dtype=np.float64)
         assert out.dtype == torch.complex128 and out.is_contiguous()
-        self.handle.call('isdf_pp_projector_overlaps', _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
+        self.handle.call(entry, _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
                          _np_ptr(coords), _np_ptr(kpt), _np_ptr(proj_tab), _np_ptr(proj_rl), len(proj_rl), _np_ptr(mesh),
                          _np_ptr(a), self._p(out))

@@ -195,6 +195,84 @@ extern "C" int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const
   return ISDF_OK;
 }
 
+// ---- three scaled row dots: the contraction of a local potential's Pulay force ------------------------------
+namespace {
+constexpr int RD_TPB = 256;
+
+// one workgroup per row m: out[x * ldo + m] (+)= alpha sum_k A_x[m, k] s[k] B[m, k]; VEC: 16-byte loads (every base 16-byte
+// aligned, every leading dimension even), the odd last column by the scalar form.  Lanes stride k; three accumulators per lane,
+// wave reduction, then the waves in order through LDS: a fixed summation order.
+template <bool VEC>
+__global__ __launch_bounds__(RD_TPB) void rowdot3_kernel(int64_t K, double alpha, const double* __restrict__ A, int64_t lda,
+                                                         int64_t astride, const double* __restrict__ s,
+                                                         const double* __restrict__ B, int64_t ldb, int accumulate,
+                                                         double* __restrict__ out, int64_t ldo) {
+  const int64_t m = blockIdx.x;
+  const double* a0 = A + m * lda;
+  const double* a1 = a0 + astride;
+  const double* a2 = a1 + astride;
+  const double* b = B + m * ldb;
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+  if (VEC) {
+    const int64_t K2 = K >> 1;
+    const double2* s2 = (const double2*)s;
+    const double2 *p0 = (const double2*)a0, *p1 = (const double2*)a1, *p2 = (const double2*)a2, *pb = (const double2*)b;
+    for (int64_t k = threadIdx.x; k < K2; k += RD_TPB) {
+      const double2 sv = s2[k], bv = pb[k], x0 = p0[k], x1 = p1[k], x2 = p2[k];
+      const double tx = sv.x * bv.x, ty = sv.y * bv.y;
+      acc0 += x0.x * tx + x0.y * ty;
+      acc1 += x1.x * tx + x1.y * ty;
+      acc2 += x2.x * tx + x2.y * ty;
+    }
+    if ((K & 1) && threadIdx.x == 0) {
+      const double t = s[K - 1] * b[K - 1];
+      acc0 += a0[K - 1] * t;
+      acc1 += a1[K - 1] * t;
+      acc2 += a2[K - 1] * t;
+    }
+  } else {
+    for (int64_t k = threadIdx.x; k < K; k += RD_TPB) {
+      const double t = s[k] * b[k];
+      acc0 += a0[k] * t;
+      acc1 += a1[k] * t;
+      acc2 += a2[k] * t;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    acc0 += __shfl_down(acc0, off, 64);
+    acc1 += __shfl_down(acc1, off, 64);
+    acc2 += __shfl_down(acc2, off, 64);
+  }
+  __shared__ double red[RD_TPB / 64][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[wave][0] = acc0; red[wave][1] = acc1; red[wave][2] = acc2; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double v = 0.0;
+    for (int w = 0; w < RD_TPB / 64; ++w) v += red[w][threadIdx.x];
+    double* o = out + threadIdx.x * ldo + m;
+    *o = accumulate ? *o + alpha * v : alpha * v;
+  }
+}
+}  // namespace
+
+extern "C" int isdf_rowdot3(isdf_handle h, int M, int64_t K, double alpha, const double* d_A, int64_t lda, int64_t astride,
+                            const double* d_s, const double* d_B, int64_t ldb, int accumulate, double* d_out, int64_t ldo) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_A && d_s && d_B && d_out && M > 0 && K > 0 && lda >= K && ldb >= K && ldo >= M && astride >= 0);
+  const bool vec = ((((uintptr_t)d_A | (uintptr_t)d_s | (uintptr_t)d_B) & 15) == 0) && ((lda | ldb | astride) & 1) == 0;
+  ProfScope ps(h, vec ? "rowdot3_kernel<true>[byte]" : "rowdot3_kernel<false>[byte]", 8.0 * (4.0 * (double)M + 1.0) * (double)K);
+  if (vec)
+    hipLaunchKernelGGL(rowdot3_kernel<true>, dim3((unsigned)M), dim3(RD_TPB), 0, h->stream, K, alpha, d_A, lda, astride, d_s, d_B,
+                       ldb, accumulate, d_out, ldo);
+  else
+    hipLaunchKernelGGL(rowdot3_kernel<false>, dim3((unsigned)M), dim3(RD_TPB), 0, h->stream, K, alpha, d_A, lda, astride, d_s,
+                       d_B, ldb, accumulate, d_out, ldo);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
 extern "C" int isdf_gemm_nn(isdf_handle h, int M, int64_t N, int K, double alpha, const double* d_A, int64_t lda,
                             const double* d_B, int64_t ldb, double beta, double* d_C, int64_t ldc) {
   if (!h) return ISDF_ERR_ARG;

@@ -6,26 +6,14 @@ from . import gto
 
 
 class HcoreMixin:
-    def get_pp(self, kpts=None):
-        """GTH pseudopotential AO matrix (G=0 removed), pyscf/pbc/df/fft.py:64-152: local part on the FFT
-        grid, non-local part from projector/AO overlaps in reciprocal space — both on the device
-        (pp.hip); only the final nproj-sized contraction with the h_ij matrices runs on the host.
-        Returns (nao,nao) for Gamma / a single k-point, else (nk,nao,nao)."""
-        cell, be = self.cell, self.backend
+    def _pp_tables(self):
+        """The device tables of the cell's GTH entries: pp_par (natm, 8) of isdf_pp_local_potential, proj_tab / proj_rl of
+        isdf_pp_projector_overlaps, blocks = (row0, l, nl, h, atom) per atom and l-channel, and the row count."""
+        cell = self.cell
         pseudo = getattr(cell, '_pseudo', None) or {}
-        if kpts is None:
-            kpts_lst, single = np.zeros((1, 3)), True
-        else:
-            kpts_lst = np.reshape(kpts, (-1, 3))
-            single = np.ndim(kpts) == 1
-        mesh = np.asarray(self.mesh, dtype=np.int32)
-        G = int(np.prod(mesh))
-        nao = cell.nao_nr()
-        a = np.asarray(cell.lattice_vectors(), dtype=float)
-        acoords = np.asarray(cell.atom_coords(), dtype=float)
         charges = np.asarray(cell.atom_charges(), dtype=float)
         pp_par = np.zeros((cell.natm, 8))
-        proj_tab, proj_rl, blocks = [], [], []          # blocks: (row0, l, nl, h) per atom and l-channel
+        proj_tab, proj_rl, blocks = [], [], []
         row = 0
         for ia in range(cell.natm):
             pp = pseudo.get(cell.atom_symbol(ia))
@@ -40,11 +28,30 @@ class HcoreMixin:
                     continue
                 if l > 2 or nl > 3:
                     raise NotImplementedError('projectors with l > 2 or more than 3 per channel')
-                blocks.append((row, l, nl, np.asarray(hl, dtype=float)))
+                blocks.append((row, l, nl, np.asarray(hl, dtype=float), ia))
                 for ii in range(nl):
                     proj_tab.append((ia, l, ii))
                     proj_rl.append(rl)
                     row += 2 * l + 1
+        return pp_par, proj_tab, proj_rl, blocks, row
+
+    def get_pp(self, kpts=None):
+        """GTH pseudopotential AO matrix (G=0 removed), pyscf/pbc/df/fft.py:64-152: local part on the FFT
+        grid, non-local part from projector/AO overlaps in reciprocal space — both on the device
+        (pp.hip); only the final nproj-sized contraction with the h_ij matrices runs on the host.
+        Returns (nao,nao) for Gamma / a single k-point, else (nk,nao,nao)."""
+        cell, be = self.cell, self.backend
+        if kpts is None:
+            kpts_lst, single = np.zeros((1, 3)), True
+        else:
+            kpts_lst = np.reshape(kpts, (-1, 3))
+            single = np.ndim(kpts) == 1
+        mesh = np.asarray(self.mesh, dtype=np.int32)
+        G = int(np.prod(mesh))
+        nao = cell.nao_nr()
+        a = np.asarray(cell.lattice_vectors(), dtype=float)
+        acoords = np.asarray(cell.atom_coords(), dtype=float)
+        pp_par, proj_tab, proj_rl, blocks, row = self._pp_tables()
         vlocR = be.empty((1, G))
         be.pp_local_potential(acoords, pp_par, mesh, a, vlocR)
         rcut = gto.estimate_rcut_per_shell(cell)
@@ -71,7 +78,7 @@ class HcoreMixin:
                                          mesh, a, ov)
                 S = be.to_host(ov)
                 vnl = np.zeros((nao, nao), dtype=np.complex128)
-                for row0, l, nl, hl in blocks:
+                for row0, l, nl, hl, _ in blocks:
                     deg = 2 * l + 1
                     blk = S[row0:row0 + nl * deg].reshape(nl, deg, nao)
                     vnl += np.einsum('imp,ij,jmq->pq', blk.conj(), hl, blk)

@@ -29,9 +29,10 @@ from .kpoints import KPointMixin
 from .hcore import HcoreMixin
 from .eri_surface import EriSurfaceMixin
 from .jk_e1 import JKE1Mixin
+from .pp_grad import PPGradMixin
 
 
-class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin, JKE1Mixin):
+class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin, JKE1Mixin, PPGradMixin):
     _keys = {'cell', 'kpts', 'grids', 'mesh', 'blockdim', 'exxdiv', 'c_isdf', 'select', 'tie_rtol'}
 
     def __init__(self, cell, kpts=np.zeros((1, 3)), c_isdf=12, select='refined', backend=None, comm=None):

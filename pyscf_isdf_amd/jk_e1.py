@@ -116,6 +116,29 @@ class JKE1Mixin:
         be.gemm_nn(self.aoP, D.T.contiguous(), left)
         return left, self.ao
 
+    def _e1_chunks(self, ncomp=4):
+        """(s0, s1, collocation (4, nao, n) of (phi, grad phi), or phi (nao, n) for ncomp = 1) over the grid in chunks of
+        e1_grid_chunk columns; the same shells, images and cutoffs as collocate().  One buffer: a chunk is valid until the next."""
+        cell, be = self.cell, self.backend
+        nao = cell.nao_nr()
+        G = int(np.prod(self.mesh))
+        chunk = max(1, min(int(self.e1_grid_chunk), G))
+        rcut = gto.estimate_rcut_per_shell(cell)
+        Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
+        ao_args = (np.asarray(cell._atm), np.asarray(cell._bas), np.asarray(cell._env), Ls, rcut)
+        coords = self.grids.coords
+        buf = be.empty((ncomp * nao * chunk,))
+        for s0 in range(0, G, chunk):
+            s1 = min(G, s0 + chunk)
+            xyz = be.to_device(np.ascontiguousarray(coords[s0:s1].T))
+            if ncomp == 1:
+                out = buf[:nao * (s1 - s0)].view(nao, s1 - s0)
+                be.eval_ao(*ao_args, xyz, out)
+            else:
+                out = buf[:4 * nao * (s1 - s0)].view(4, nao, s1 - s0)
+                be.eval_ao_deriv1(*ao_args, xyz, out)
+            yield s0, s1, out
+
     def _e1_walk(self, dms, with_j, with_k):
         """(vj, vk), each (nset, 3, nao, nao) on the host or None, of real density matrices dms (nset, nao, nao)."""
         cell, be = self.cell, self.backend
@@ -125,23 +148,6 @@ class JKE1Mixin:
         a = np.asarray(cell.lattice_vectors(), dtype=float)
         w = cell.vol / G
         chunk = max(1, min(int(self.e1_grid_chunk), G))
-        # the same shells, images and cutoffs as collocate()
-        rcut = gto.estimate_rcut_per_shell(cell)
-        Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
-        ao_args = (np.asarray(cell._atm), np.asarray(cell._bas), np.asarray(cell._env), Ls, rcut)
-        coords = self.grids.coords
-        ao4_buf = be.empty((4 * nao * chunk,))
-
-        def collocate(s0, s1, ncomp=4):
-            xyz = be.to_device(np.ascontiguousarray(coords[s0:s1].T))
-            if ncomp == 1:
-                out = ao4_buf[:nao * (s1 - s0)].view(nao, s1 - s0)
-                be.eval_ao(*ao_args, xyz, out)
-            else:
-                out = ao4_buf[:4 * nao * (s1 - s0)].view(4, nao, s1 - s0)
-                be.eval_ao_deriv1(*ao_args, xyz, out)
-            return out
-
         t0 = time.perf_counter()
         d_vj = vJ = None
         if with_j:
@@ -151,9 +157,7 @@ class JKE1Mixin:
             if self.ao is not None:
                 be.rho_pair(self.ao, self.ao, G, d_sym, vJ)
             else:
-                for s0 in range(0, G, chunk):
-                    s1 = min(G, s0 + chunk)
-                    phi = collocate(s0, s1, 1)
+                for s0, s1, phi in self._e1_chunks(1):
                     be.rho_pair(phi, phi, s1 - s0, d_sym, vJ[:, s0:s1])
             be.coulomb_rows(vJ, mesh, a, nset)
             d_vj = be.zeros((nset, 3, nao, nao))
@@ -170,10 +174,8 @@ class JKE1Mixin:
             nb = max(1, min(P, nb))
             F_buf = be.empty((nb * chunk,))
             t0 = self._tick('S8_get_k_e1', t0)
-        for s0 in range(0, G, chunk):
-            s1 = min(G, s0 + chunk)
+        for s0, s1, dao in self._e1_chunks():
             n = s1 - s0
-            dao = collocate(s0, s1)
             if with_j:
                 for s in range(nset):
                     ks = vJ[s, s0:s1]

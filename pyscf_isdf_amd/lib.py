@@ -98,6 +98,10 @@ SIGNATURES = {
     'isdf_vj_k': (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_vp]),
     'isdf_pp_local_potential': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'isdf_pp_projector_overlaps': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    'isdf_pp_local_force': (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'isdf_pp_projector_overlaps_ip': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                              c_vp]),
+    'isdf_rowdot3': (c_int, [c_vp, c_int, c_i64, c_dbl, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_int, c_vp, c_i64]),
     'isdf_gemm_nn': (c_int, [c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_i64, c_vp, c_i64, c_dbl, c_vp, c_i64]),
     'isdf_hadamard_rows': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_i64]),
     'isdf_eval_ao_deriv1': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64]),
