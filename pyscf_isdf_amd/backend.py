@@ -142,46 +142,48 @@ class HipBackend:
         return _vp(t.data_ptr())          # data_ptr() of a view already points at its first element
 
     # ---- stages -------------------------------------------------------------------------------
+    @staticmethod
+    def _ao_tables(atm, bas, env, Ls, rcut):
+        """The pointer / length arguments that open every isdf_eval_ao* call, on the basis tables converted as the library reads
+        them.  Each pointer keeps its array referenced (ndarray.ctypes.data_as), so the tables live as long as the tuple does."""
+        atm, bas = np.ascontiguousarray(atm, dtype=np.int32), np.ascontiguousarray(bas, dtype=np.int32)
+        env, Ls, rcut = (np.ascontiguousarray(x, dtype=np.float64) for x in (env, Ls, rcut))
+        return _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env), _np_ptr(Ls), len(Ls), _np_ptr(rcut)
+
     def eval_ao(self, atm, bas, env, Ls, rcut, coords_soa, ao):
         """ao (nao, ld) <- collocation on coords_soa (3, G)."""
         self._stream()
-        atm = np.ascontiguousarray(atm, dtype=np.int32)
-        bas = np.ascontiguousarray(bas, dtype=np.int32)
-        env = np.ascontiguousarray(env, dtype=np.float64)
-        Ls = np.ascontiguousarray(Ls, dtype=np.float64)
-        rcut = np.ascontiguousarray(rcut, dtype=np.float64)
+        tables = self._ao_tables(atm, bas, env, Ls, rcut)
         G = coords_soa.shape[1]
         assert coords_soa.is_contiguous() and ao.stride(1) == 1 and ao.shape[1] >= G
-        self.handle.call('isdf_eval_ao', _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
-                         _np_ptr(Ls), len(Ls), _np_ptr(rcut), self._p(coords_soa), G, self._p(ao), ao.stride(0))
+        self.handle.call('isdf_eval_ao', *tables, self._p(coords_soa), G, self._p(ao), ao.stride(0))
 
     def eval_ao_deriv1(self, atm, bas, env, Ls, rcut, coords_soa, ao4):
         """ao4 (4, nao, ld) <- values and x, y, z derivatives on coords_soa (3, G)."""
         self._stream()
-        atm = np.ascontiguousarray(atm, dtype=np.int32)
-        bas = np.ascontiguousarray(bas, dtype=np.int32)
-        env = np.ascontiguousarray(env, dtype=np.float64)
-        Ls = np.ascontiguousarray(Ls, dtype=np.float64)
-        rcut = np.ascontiguousarray(rcut, dtype=np.float64)
+        tables = self._ao_tables(atm, bas, env, Ls, rcut)
         G = coords_soa.shape[1]
         assert coords_soa.is_contiguous() and ao4.dim() == 3 and ao4.shape[0] == 4 and ao4.stride(2) == 1 and ao4.shape[2] >= G
-        self.handle.call('isdf_eval_ao_deriv1', _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
-                         _np_ptr(Ls), len(Ls), _np_ptr(rcut), self._p(coords_soa), G, self._p(ao4), ao4.stride(1), ao4.stride(0))
+        self.handle.call('isdf_eval_ao_deriv1', *tables, self._p(coords_soa), G, self._p(ao4), ao4.stride(1), ao4.stride(0))
+
+    def eval_ao_k(self, atm, bas, env, Ls, rcut, kpt, periodic_part, coords_soa, out_re, out_im):
+        self._stream()
+        tables = self._ao_tables(atm, bas, env, Ls, rcut)
+        kpt = np.ascontiguousarray(kpt, dtype=np.float64)
+        G = coords_soa.shape[1]
+        assert out_re.stride(0) == out_im.stride(0) and out_re.stride(1) == 1
+        self.handle.call('isdf_eval_ao_k', *tables, _np_ptr(kpt), int(bool(periodic_part)), self._p(coords_soa), G,
+                         self._p(out_re), self._p(out_im), out_re.stride(0))
 
     def eval_ao_k_deriv1(self, atm, bas, env, Ls, rcut, kpt, periodic_part, coords_soa, out_re, out_im):
         """out_re / out_im (4, nao, ld) views of one buffer <- Bloch sums of values and x, y, z derivatives at ``kpt``."""
         self._stream()
-        atm = np.ascontiguousarray(atm, dtype=np.int32)
-        bas = np.ascontiguousarray(bas, dtype=np.int32)
-        env = np.ascontiguousarray(env, dtype=np.float64)
-        Ls = np.ascontiguousarray(Ls, dtype=np.float64)
-        rcut = np.ascontiguousarray(rcut, dtype=np.float64)
+        tables = self._ao_tables(atm, bas, env, Ls, rcut)
         kpt = np.ascontiguousarray(kpt, dtype=np.float64)
         G = coords_soa.shape[1]
         assert out_re.dim() == 3 and out_re.shape[0] == 4 and tuple(out_re.shape) == tuple(out_im.shape)
         assert out_re.stride() == out_im.stride() and out_re.stride(2) == 1 and out_re.shape[2] >= G
-        self.handle.call('isdf_eval_ao_k_deriv1', _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
-                         _np_ptr(Ls), len(Ls), _np_ptr(rcut), _np_ptr(kpt), int(bool(periodic_part)), self._p(coords_soa), G,
+        self.handle.call('isdf_eval_ao_k_deriv1', *tables, _np_ptr(kpt), int(bool(periodic_part)), self._p(coords_soa), G,
                          self._p(out_re), self._p(out_im), out_re.stride(1), out_re.stride(0))
 
     def gather_cols(self, src, idx, dst):
@@ -694,20 +696,6 @@ class HipBackend:
         return out.value
 
     # ---- k-points -----------------------------------------------------------------------------
-    def eval_ao_k(self, atm, bas, env, Ls, rcut, kpt, periodic_part, coords_soa, out_re, out_im):
-        self._stream()
-        atm = np.ascontiguousarray(atm, dtype=np.int32)
-        bas = np.ascontiguousarray(bas, dtype=np.int32)
-        env = np.ascontiguousarray(env, dtype=np.float64)
-        Ls = np.ascontiguousarray(Ls, dtype=np.float64)
-        rcut = np.ascontiguousarray(rcut, dtype=np.float64)
-        kpt = np.ascontiguousarray(kpt, dtype=np.float64)
-        G = coords_soa.shape[1]
-        assert out_re.stride(0) == out_im.stride(0) and out_re.stride(1) == 1
-        self.handle.call('isdf_eval_ao_k', _np_ptr(atm), len(atm), _np_ptr(bas), len(bas), _np_ptr(env), len(env),
-                         _np_ptr(Ls), len(Ls), _np_ptr(rcut), _np_ptr(kpt), int(bool(periodic_part)), self._p(coords_soa), G,
-                         self._p(out_re), self._p(out_im), out_re.stride(0))
-
     def select_ip_cplx(self, X, nh, blk_off, nip, tol, tie_rtol, L, piv):
         self._stream()
         blk_off = np.ascontiguousarray(blk_off, dtype=np.int64)

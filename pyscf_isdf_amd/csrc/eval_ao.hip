@@ -1,4 +1,5 @@
-// S1: periodic AO collocation on gfx950 (Γ point, real spherical GTOs, l <= 3).
+// S1: periodic AO collocation on gfx950 (real spherical GTOs, l <= 3): values and Cartesian first derivatives, at the Γ point
+// or as Bloch sums at a k-point.  Four kernels, one body (eval_ao_body -> cull_images, shell_eval).
 //
 // One workgroup = 256 consecutive grid points x one atom.  The workgroup first culls the lattice
 // translations against the bounding box of its points (LDS list), then every lane walks only the
@@ -101,316 +102,8 @@ __device__ inline double wave_max(double v) {
   return v;
 }
 
-template <int L>
-__device__ inline void shell_eval(const ShellDev sh, const double* __restrict__ env,
-                                  const double* __restrict__ Ls, const int* __restrict__ img_list,
-                                  int nlist, double px, double py, double pz, double ax, double ay,
-                                  double az, bool valid, double* __restrict__ ao, int64_t ld,
-                                  int64_t g) {
-  constexpr int DEG = 2 * L + 1;
-  double acc[NCMAX][DEG];
-#pragma unroll
-  for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-    for (int m = 0; m < DEG; ++m) acc[c][m] = 0.0;
-  const double fac = (L == 0) ? FAC_S : (L == 1 ? FAC_P : 1.0);
-  const double* __restrict__ es = env + sh.pexp;
-  const double* __restrict__ cs = env + sh.pcoef;
-  for (int i = 0; i < nlist; ++i) {
-    const int iL = img_list[i];
-    const double dx = px - (ax + Ls[3 * iL + 0]);
-    const double dy = py - (ay + Ls[3 * iL + 1]);
-    const double dz = pz - (az + Ls[3 * iL + 2]);
-    const double rr = dx * dx + dy * dy + dz * dz;
-    if (rr < sh.rcut2) {
-      double rad[NCMAX];
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c) rad[c] = 0.0;
-      for (int p = 0; p < sh.nprim; ++p) {
-        const double e = exp(-es[p] * rr) * fac;
-#pragma unroll
-        for (int c = 0; c < NCMAX; ++c)
-          if (c < sh.nctr) rad[c] += cs[c * sh.nprim + p] * e;
-      }
-      double ang[DEG];
-      angular<L>(dx, dy, dz, ang);
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-        for (int m = 0; m < DEG; ++m) acc[c][m] += rad[c] * ang[m];
-    }
-  }
-  if (valid) {
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-      if (c < sh.nctr) {
-#pragma unroll
-        for (int m = 0; m < DEG; ++m) ao[(int64_t)(sh.ao0 + c * DEG + m) * ld + g] = acc[c][m];
-      }
-  }
-}
-
-__global__ __launch_bounds__(TPB) void eval_ao_kernel(
-    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
-    const double* __restrict__ env, const double* __restrict__ Ls, int nimgs,
-    const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao, int64_t ld) {
-  extern __shared__ int img_list[];      // nimgs ints
-  __shared__ double red[6][TPB / 64];
-  __shared__ int wcnt[TPB / 64];
-  const int tid = threadIdx.x;
-  const int64_t g = (int64_t)blockIdx.x * TPB + tid;
-  const bool valid = g < ngrids;
-  const int64_t gc = valid ? g : (int64_t)blockIdx.x * TPB;   // clamp to the block's first point
-  const double px = coords[gc], py = coords[ngrids + gc], pz = coords[2 * ngrids + gc];
-  const AtomDev at = atoms[blockIdx.y];
-
-  // bounding box of the workgroup's points
-  double lo[3] = {wave_min(px), wave_min(py), wave_min(pz)};
-  double hi[3] = {wave_max(px), wave_max(py), wave_max(pz)};
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) {
-    for (int k = 0; k < 3; ++k) { red[k][w] = lo[k]; red[3 + k][w] = hi[k]; }
-  }
-  __syncthreads();
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = red[k][0]; hi[k] = red[3 + k][0];
-    for (int ww = 1; ww < TPB / 64; ++ww) {
-      lo[k] = fmin(lo[k], red[k][ww]);
-      hi[k] = fmax(hi[k], red[3 + k][ww]);
-    }
-  }
-  // cull images: keep T when dist(R + T, box) < rcut_max (conservative; the exact test is per
-  // point).  Ordered compaction (ballot + prefix) keeps the list in ascending image index, so the
-  // floating-point accumulation order over images is fixed and equals the oracle's.
-  const double rc2 = at.rcut_max * at.rcut_max;
-  const int lane = tid & 63;
-  int nlist = 0;
-  for (int base = 0; base < nimgs; base += TPB) {
-    const int i = base + tid;
-    bool keep = false;
-    if (i < nimgs) {
-      const double c[3] = {at.x + Ls[3 * i], at.y + Ls[3 * i + 1], at.z + Ls[3 * i + 2]};
-      double d2 = 0.0;
-      for (int k = 0; k < 3; ++k) {
-        const double d = fmax(fmax(lo[k] - c[k], c[k] - hi[k]), 0.0);
-        d2 += d * d;
-      }
-      keep = d2 < rc2;
-    }
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wcnt[w] = __popcll(mask);
-    __syncthreads();
-    int off = nlist;
-    for (int ww = 0; ww < w; ++ww) off += wcnt[ww];
-    if (keep) img_list[off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-    for (int ww = 0; ww < TPB / 64; ++ww) nlist += wcnt[ww];
-    __syncthreads();
-  }
-
-  for (int s = at.sh0; s < at.sh1; ++s) {
-    const ShellDev sh = shells[s];
-    switch (sh.l) {
-      case 0: shell_eval<0>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, g); break;
-      case 1: shell_eval<1>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, g); break;
-      case 2: shell_eval<2>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, g); break;
-      default: shell_eval<3>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, g); break;
-    }
-  }
-}
-
-// k-point variant: every image contributes with the Bloch factor exp(i k.T) (table per image), the
-// result is multiplied by exp(-i k.r) to give the lattice-periodic part u^k = exp(-i k.r) phi^k
-// (periodic=1) or left as phi^k (periodic=0).  Output: real and imaginary planes.
-template <int L>
-__device__ inline void shell_eval_k(const ShellDev sh, const double* __restrict__ env,
-                                    const double* __restrict__ Ls, const double* __restrict__ phT,
-                                    const int* __restrict__ img_list, int nlist, double px, double py,
-                                    double pz, double ax, double ay, double az, bool valid, double pr,
-                                    double pi, double* __restrict__ out_re, double* __restrict__ out_im,
-                                    int64_t ld, int64_t g) {
-  constexpr int DEG = 2 * L + 1;
-  double accr[NCMAX][DEG], acci[NCMAX][DEG];
-#pragma unroll
-  for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-    for (int m = 0; m < DEG; ++m) { accr[c][m] = 0.0; acci[c][m] = 0.0; }
-  const double fac = (L == 0) ? FAC_S : (L == 1 ? FAC_P : 1.0);
-  const double* __restrict__ es = env + sh.pexp;
-  const double* __restrict__ cs = env + sh.pcoef;
-  for (int i = 0; i < nlist; ++i) {
-    const int iL = img_list[i];
-    const double dx = px - (ax + Ls[3 * iL + 0]);
-    const double dy = py - (ay + Ls[3 * iL + 1]);
-    const double dz = pz - (az + Ls[3 * iL + 2]);
-    const double rr = dx * dx + dy * dy + dz * dz;
-    if (rr < sh.rcut2) {
-      const double tr = phT[2 * iL], ti = phT[2 * iL + 1];
-      double rad[NCMAX];
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c) rad[c] = 0.0;
-      for (int p = 0; p < sh.nprim; ++p) {
-        const double e = exp(-es[p] * rr) * fac;
-#pragma unroll
-        for (int c = 0; c < NCMAX; ++c)
-          if (c < sh.nctr) rad[c] += cs[c * sh.nprim + p] * e;
-      }
-      double ang[DEG];
-      angular<L>(dx, dy, dz, ang);
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-        for (int m = 0; m < DEG; ++m) {
-          const double v = rad[c] * ang[m];
-          accr[c][m] += v * tr;
-          acci[c][m] += v * ti;
-        }
-    }
-  }
-  if (valid) {
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-      if (c < sh.nctr) {
-#pragma unroll
-        for (int m = 0; m < DEG; ++m) {
-          const int64_t off = (int64_t)(sh.ao0 + c * DEG + m) * ld + g;
-          out_re[off] = accr[c][m] * pr - acci[c][m] * pi;
-          out_im[off] = accr[c][m] * pi + acci[c][m] * pr;
-        }
-      }
-  }
-}
-
-__global__ __launch_bounds__(TPB) void eval_ao_k_kernel(
-    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
-    const double* __restrict__ env, const double* __restrict__ Ls, const double* __restrict__ phT,
-    int nimgs, double kx, double ky, double kz, int periodic, const double* __restrict__ coords,
-    int64_t ngrids, double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld) {
-  extern __shared__ int img_list[];
-  __shared__ double red[6][TPB / 64];
-  __shared__ int wcnt[TPB / 64];
-  const int tid = threadIdx.x;
-  const int64_t g = (int64_t)blockIdx.x * TPB + tid;
-  const bool valid = g < ngrids;
-  const int64_t gc = valid ? g : (int64_t)blockIdx.x * TPB;
-  const double px = coords[gc], py = coords[ngrids + gc], pz = coords[2 * ngrids + gc];
-  const AtomDev at = atoms[blockIdx.y];
-  double lo[3] = {wave_min(px), wave_min(py), wave_min(pz)};
-  double hi[3] = {wave_max(px), wave_max(py), wave_max(pz)};
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) {
-    for (int k = 0; k < 3; ++k) { red[k][w] = lo[k]; red[3 + k][w] = hi[k]; }
-  }
-  __syncthreads();
-  for (int k = 0; k < 3; ++k) {
-    lo[k] = red[k][0]; hi[k] = red[3 + k][0];
-    for (int ww = 1; ww < TPB / 64; ++ww) {
-      lo[k] = fmin(lo[k], red[k][ww]);
-      hi[k] = fmax(hi[k], red[3 + k][ww]);
-    }
-  }
-  const double rc2 = at.rcut_max * at.rcut_max;
-  const int lane = tid & 63;
-  int nlist = 0;
-  for (int base = 0; base < nimgs; base += TPB) {
-    const int i = base + tid;
-    bool keep = false;
-    if (i < nimgs) {
-      const double c[3] = {at.x + Ls[3 * i], at.y + Ls[3 * i + 1], at.z + Ls[3 * i + 2]};
-      double d2 = 0.0;
-      for (int k = 0; k < 3; ++k) {
-        const double d = fmax(fmax(lo[k] - c[k], c[k] - hi[k]), 0.0);
-        d2 += d * d;
-      }
-      keep = d2 < rc2;
-    }
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) wcnt[w] = __popcll(mask);
-    __syncthreads();
-    int off = nlist;
-    for (int ww = 0; ww < w; ++ww) off += wcnt[ww];
-    if (keep) img_list[off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-    for (int ww = 0; ww < TPB / 64; ++ww) nlist += wcnt[ww];
-    __syncthreads();
-  }
-  // exp(-i k.r) for the periodic part (1 otherwise)
-  double pr = 1.0, pi = 0.0;
-  if (periodic) {
-    const double kr = kx * px + ky * py + kz * pz;
-    sincos(-kr, &pi, &pr);
-  }
-  for (int s = at.sh0; s < at.sh1; ++s) {
-    const ShellDev sh = shells[s];
-    switch (sh.l) {
-      case 0: shell_eval_k<0>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, g); break;
-      case 1: shell_eval_k<1>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, g); break;
-      case 2: shell_eval_k<2>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, g); break;
-      default: shell_eval_k<3>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, g); break;
-    }
-  }
-}
-
-// Values and Cartesian first derivatives (GGA densities and potentials; numint.eval_ao(deriv=1), pyscf/lib/gto/deriv1.c:60-69 for
-// the radial part): phi = fac ang(d) R(r^2), R = sum_p c_p exp(-a_p r^2)  ->  grad phi = grad(ang) R - 2 d ang R1,
-// R1 = sum_p c_p a_p exp(-a_p r^2).  Four output planes (value, d/dx, d/dy, d/dz), each AO-major like eval_ao_kernel's.
-template <int L>
-__device__ inline void shell_eval_d1(const ShellDev sh, const double* __restrict__ env, const double* __restrict__ Ls,
-                                     const int* __restrict__ img_list, int nlist, double px, double py, double pz, double ax,
-                                     double ay, double az, bool valid, double* __restrict__ ao, int64_t ld, int64_t plane,
-                                     int64_t g) {
-  constexpr int DEG = 2 * L + 1;
-  double acc[4][NCMAX][DEG];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-      for (int m = 0; m < DEG; ++m) acc[x][c][m] = 0.0;
-  const double fac = (L == 0) ? FAC_S : (L == 1 ? FAC_P : 1.0);
-  const double* __restrict__ es = env + sh.pexp;
-  const double* __restrict__ cs = env + sh.pcoef;
-  for (int i = 0; i < nlist; ++i) {
-    const int iL = img_list[i];
-    const double d[3] = {px - (ax + Ls[3 * iL + 0]), py - (ay + Ls[3 * iL + 1]), pz - (az + Ls[3 * iL + 2])};
-    const double rr = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    if (rr < sh.rcut2) {
-      double rad[NCMAX], rad1[NCMAX];
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c) { rad[c] = 0.0; rad1[c] = 0.0; }
-      for (int p = 0; p < sh.nprim; ++p) {
-        const double e = exp(-es[p] * rr) * fac;
-#pragma unroll
-        for (int c = 0; c < NCMAX; ++c)
-          if (c < sh.nctr) {
-            rad[c] += cs[c * sh.nprim + p] * e;
-            rad1[c] += cs[c * sh.nprim + p] * es[p] * e;
-          }
-      }
-      double ang[DEG], gang[DEG][3];
-      angular_grad<L>(d, ang, gang);
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c)
-#pragma unroll
-        for (int m = 0; m < DEG; ++m) {
-          acc[0][c][m] += rad[c] * ang[m];
-#pragma unroll
-          for (int x = 0; x < 3; ++x) acc[1 + x][c][m] += gang[m][x] * rad[c] - 2.0 * d[x] * ang[m] * rad1[c];
-        }
-    }
-  }
-  if (valid) {
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-      for (int c = 0; c < NCMAX; ++c)
-        if (c < sh.nctr) {
-#pragma unroll
-          for (int m = 0; m < DEG; ++m) ao[x * plane + (int64_t)(sh.ao0 + c * DEG + m) * ld + g] = acc[x][c][m];
-        }
-  }
-}
-
-// the workgroup's image list (see eval_ao_kernel): ordered compaction of the translations whose atom image can reach the
-// bounding box of the workgroup's points; returns the list length
+// the workgroup's image list: ordered compaction of the translations whose atom image can reach the bounding box of the
+// workgroup's points; returns the list length
 __device__ inline int cull_images(const AtomDev at, const double* __restrict__ Ls, int nimgs, double px, double py, double pz,
                                   int* __restrict__ img_list, double (*red)[TPB / 64], int* __restrict__ wcnt) {
   const int tid = threadIdx.x;
@@ -428,6 +121,9 @@ __device__ inline int cull_images(const AtomDev at, const double* __restrict__ L
       hi[k] = fmax(hi[k], red[3 + k][ww]);
     }
   }
+  // keep T when dist(R + T, box) < rcut_max (conservative; the exact test is per point).  Ordered compaction (ballot + prefix)
+  // keeps the list in ascending image index, so the floating-point accumulation order over images is fixed and equals the
+  // oracle's.
   const double rc2 = at.rcut_max * at.rcut_max;
   const int lane = tid & 63;
   int nlist = 0;
@@ -455,54 +151,55 @@ __device__ inline int cull_images(const AtomDev at, const double* __restrict__ L
   return nlist;
 }
 
-__global__ __launch_bounds__(TPB) void eval_ao_deriv1_kernel(
-    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells, const double* __restrict__ env,
-    const double* __restrict__ Ls, int nimgs, const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao,
-    int64_t ld, int64_t plane) {
-  extern __shared__ int img_list[];
-  __shared__ double red[6][TPB / 64];
-  __shared__ int wcnt[TPB / 64];
-  const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
-  const bool valid = g < ngrids;
-  const int64_t gc = valid ? g : (int64_t)blockIdx.x * TPB;
-  const double px = coords[gc], py = coords[ngrids + gc], pz = coords[2 * ngrids + gc];
-  const AtomDev at = atoms[blockIdx.y];
-  const int nlist = cull_images(at, Ls, nimgs, px, py, pz, img_list, red, wcnt);
-  for (int s = at.sh0; s < at.sh1; ++s) {
-    const ShellDev sh = shells[s];
-    switch (sh.l) {
-      case 0: shell_eval_d1<0>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, plane, g); break;
-      case 1: shell_eval_d1<1>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, plane, g); break;
-      case 2: shell_eval_d1<2>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, plane, g); break;
-      default: shell_eval_d1<3>(sh, env, Ls, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, ao, ld, plane, g); break;
-    }
-  }
-}
+// a lane's grid point: coordinates, column g of the output (written when valid) and exp(-i k.r) for the periodic part (1 otherwise)
+struct Point {
+  double px, py, pz;
+  int64_t g;
+  bool valid;
+  double pr, pi;
+};
+// output planes of a pass, starting at its first component: the pass's component x of AO row r goes to re[x * plane + r * ld + g]
+// (im: the imaginary planes of the k forms)
+struct Out {
+  double* re;
+  double* im;
+  int64_t ld, plane;
+  __device__ Out from(int x) const { return Out{re + x * plane, im + x * plane, ld, plane}; }
+};
 
-// k-point form of shell_eval_d1, one component X (0 value, 1..3 d/dx, d/dy, d/dz) per call so that the accumulators stay in
-// registers: Bloch sums sum_T exp(i k.T) (.)(r - T) of the value or of one derivative, times exp(-i k.r) when the periodic part is
-// asked for (then the derivative is that of the Bloch function times the phase, NOT the derivative of the periodic part - callers
-// that differentiate pair products conj(u_i) u_j never see the difference: the phases cancel in the product and in its gradient).
-template <int L, int X>
-__device__ inline void shell_eval_k_d1(const ShellDev sh, const double* __restrict__ env, const double* __restrict__ Ls,
-                                       const double* __restrict__ phT, const int* __restrict__ img_list, int nlist, double px,
-                                       double py, double pz, double ax, double ay, double az, bool valid, double pr, double pi,
-                                       double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld, int64_t g) {
+// One shell on the workgroup's image list: components X0 .. X0 + NX - 1 (0 the value, 1..3 d/dx, d/dy, d/dz) of
+//   phi = fac ang(d) R(r^2), R = sum_p c_p exp(-a_p r^2);  grad phi = grad(ang) R - 2 d ang R1, R1 = sum_p c_p a_p exp(-a_p r^2)
+// (numint.eval_ao(deriv=1), pyscf/lib/gto/deriv1.c:60-69 for the radial part), summed over the images - plainly (Gamma) or, CPLX,
+// with the Bloch factor exp(i k.T) of the table phT and multiplied at the store by the point's exp(-i k.r): the lattice-periodic
+// part u^k = exp(-i k.r) phi^k, or phi^k itself when that factor is 1.  A derivative is then that of the Bloch function times the
+// phase, NOT the derivative of the periodic part - callers that differentiate pair products conj(u_i) u_j never see the
+// difference: the phases cancel in the product and in its gradient.  The accumulators of all NX components stay in registers.
+template <int L, bool CPLX, int X0, int NX>
+__device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const double* __restrict__ env, const double* __restrict__ Ls,
+                                  const double* __restrict__ phT, const int* __restrict__ img_list, int nlist, const Point pt,
+                                  const Out out) {
   constexpr int DEG = 2 * L + 1;
-  double accr[NCMAX][DEG], acci[NCMAX][DEG];
+  constexpr bool D1 = X0 + NX > 1;       // a derivative component is among them: rad1 and the angular gradients are needed
+  double accr[NX][NCMAX][DEG], acci[CPLX ? NX : 1][NCMAX][DEG];
 #pragma unroll
-  for (int c = 0; c < NCMAX; ++c)
+  for (int x = 0; x < NX; ++x)
 #pragma unroll
-    for (int m = 0; m < DEG; ++m) { accr[c][m] = 0.0; acci[c][m] = 0.0; }
+    for (int c = 0; c < NCMAX; ++c)
+#pragma unroll
+      for (int m = 0; m < DEG; ++m) {
+        accr[x][c][m] = 0.0;
+        if (CPLX) acci[x][c][m] = 0.0;
+      }
   const double fac = (L == 0) ? FAC_S : (L == 1 ? FAC_P : 1.0);
   const double* __restrict__ es = env + sh.pexp;
   const double* __restrict__ cs = env + sh.pcoef;
   for (int i = 0; i < nlist; ++i) {
     const int iL = img_list[i];
-    const double d[3] = {px - (ax + Ls[3 * iL + 0]), py - (ay + Ls[3 * iL + 1]), pz - (az + Ls[3 * iL + 2])};
+    const double d[3] = {pt.px - (at.x + Ls[3 * iL + 0]), pt.py - (at.y + Ls[3 * iL + 1]), pt.pz - (at.z + Ls[3 * iL + 2])};
     const double rr = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
     if (rr < sh.rcut2) {
-      const double tr = phT[2 * iL], ti = phT[2 * iL + 1];
+      double tr = 1.0, ti = 0.0;
+      if (CPLX) { tr = phT[2 * iL]; ti = phT[2 * iL + 1]; }
       double rad[NCMAX], rad1[NCMAX];
 #pragma unroll
       for (int c = 0; c < NCMAX; ++c) { rad[c] = 0.0; rad1[c] = 0.0; }
@@ -512,47 +209,123 @@ __device__ inline void shell_eval_k_d1(const ShellDev sh, const double* __restri
         for (int c = 0; c < NCMAX; ++c)
           if (c < sh.nctr) {
             rad[c] += cs[c * sh.nprim + p] * e;
-            if (X > 0) rad1[c] += cs[c * sh.nprim + p] * es[p] * e;
+            if (D1) rad1[c] += cs[c * sh.nprim + p] * es[p] * e;
           }
       }
-      double ang[DEG], gang[DEG], g3[DEG][3];
-      angular_grad<L>(d, ang, g3);                  // (the two unused gradient components are dead code after inlining)
+      double ang[DEG], gang[DEG][3];
+      if (D1) angular_grad<L>(d, ang, gang);
+      else angular<L>(d[0], d[1], d[2], ang);
+      // every accumulator has its own sum, so the order of these three loops changes no bit; m, c, x is the one measured: with the
+      // component innermost under c, m the Gamma gradient pass takes 24 more VGPRs, with it outermost it runs 0.8 % slower
 #pragma unroll
-      for (int m = 0; m < DEG; ++m) gang[m] = g3[m][X > 0 ? X - 1 : 0];
+      for (int m = 0; m < DEG; ++m)
 #pragma unroll
-      for (int c = 0; c < NCMAX; ++c)
+        for (int c = 0; c < NCMAX; ++c)
 #pragma unroll
-        for (int m = 0; m < DEG; ++m) {
-          const double v = (X == 0) ? rad[c] * ang[m] : gang[m] * rad[c] - 2.0 * d[X > 0 ? X - 1 : 0] * ang[m] * rad1[c];
-          accr[c][m] += v * tr;
-          acci[c][m] += v * ti;
-        }
+          for (int x = 0; x < NX; ++x) {
+            const int k = X0 + x > 0 ? X0 + x - 1 : 0;       // Cartesian direction of a derivative component
+            const double v = (X0 + x == 0) ? rad[c] * ang[m] : gang[m][k] * rad[c] - 2.0 * d[k] * ang[m] * rad1[c];
+            if (CPLX) {
+              accr[x][c][m] += v * tr;
+              acci[x][c][m] += v * ti;
+            } else {
+              accr[x][c][m] += v;
+            }
+          }
     }
   }
-  if (valid) {
+  if (pt.valid) {
 #pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-      if (c < sh.nctr) {
+    for (int x = 0; x < NX; ++x)
 #pragma unroll
-        for (int m = 0; m < DEG; ++m) {
-          const int64_t off = (int64_t)(sh.ao0 + c * DEG + m) * ld + g;
-          out_re[off] = accr[c][m] * pr - acci[c][m] * pi;
-          out_im[off] = accr[c][m] * pi + acci[c][m] * pr;
+      for (int c = 0; c < NCMAX; ++c)
+        if (c < sh.nctr) {
+#pragma unroll
+          for (int m = 0; m < DEG; ++m) {
+            const int64_t off = x * out.plane + (int64_t)(sh.ao0 + c * DEG + m) * out.ld + pt.g;
+            if (CPLX) {
+              out.re[off] = accr[x][c][m] * pt.pr - acci[x][c][m] * pt.pi;
+              out.im[off] = accr[x][c][m] * pt.pi + acci[x][c][m] * pt.pr;
+            } else {
+              out.re[off] = accr[x][c][m];
+            }
+          }
         }
-      }
   }
 }
 
-template <int L>
-__device__ inline void shell_eval_k_d1_all(const ShellDev sh, const double* __restrict__ env, const double* __restrict__ Ls,
-                                           const double* __restrict__ phT, const int* __restrict__ img_list, int nlist, double px,
-                                           double py, double pz, double ax, double ay, double az, bool valid, double pr, double pi,
-                                           double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld, int64_t plane,
-                                           int64_t g) {
-  shell_eval_k_d1<L, 0>(sh, env, Ls, phT, img_list, nlist, px, py, pz, ax, ay, az, valid, pr, pi, out_re, out_im, ld, g);
-  shell_eval_k_d1<L, 1>(sh, env, Ls, phT, img_list, nlist, px, py, pz, ax, ay, az, valid, pr, pi, out_re + plane, out_im + plane, ld, g);
-  shell_eval_k_d1<L, 2>(sh, env, Ls, phT, img_list, nlist, px, py, pz, ax, ay, az, valid, pr, pi, out_re + 2 * plane, out_im + 2 * plane, ld, g);
-  shell_eval_k_d1<L, 3>(sh, env, Ls, phT, img_list, nlist, px, py, pz, ax, ay, az, valid, pr, pi, out_re + 3 * plane, out_im + 3 * plane, ld, g);
+// the instantiations of a form: values in one pass; Gamma gradients all four components in one pass; Bloch gradients one
+// component per pass, which keeps the complex accumulators in registers
+template <int L, bool CPLX, bool D1>
+__device__ inline void shell_form(const ShellDev sh, const AtomDev at, const double* __restrict__ env, const double* __restrict__ Ls,
+                                  const double* __restrict__ phT, const int* __restrict__ img_list, int nlist, const Point pt,
+                                  const Out out) {
+  if constexpr (!D1) {
+    shell_eval<L, CPLX, 0, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
+  } else if constexpr (!CPLX) {
+    shell_eval<L, false, 0, 4>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
+  } else {
+    shell_eval<L, true, 0, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
+    shell_eval<L, true, 1, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(1));
+    shell_eval<L, true, 2, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(2));
+    shell_eval<L, true, 3, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(3));
+  }
+}
+
+// The body of the four kernels: one workgroup = 256 consecutive grid points x one atom.  Load the point, cull the images against
+// the workgroup's box, take the point's phase, then walk the atom's shells.  Output AO-major: (nao, ld) planes, four of them
+// (value, d/dx, d/dy, d/dz) at stride out.plane for the derivative forms, a real and an imaginary set for the k forms.
+template <bool CPLX, bool D1>
+__device__ __forceinline__ void eval_ao_body(const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
+                                             const double* __restrict__ env, const double* __restrict__ Ls,
+                                             const double* __restrict__ phT, int nimgs, double kx, double ky, double kz, int periodic,
+                                             const double* __restrict__ coords, int64_t ngrids, const Out out) {
+  extern __shared__ int img_list[];      // nimgs ints
+  __shared__ double red[6][TPB / 64];
+  __shared__ int wcnt[TPB / 64];
+  Point pt;
+  pt.g = (int64_t)blockIdx.x * TPB + threadIdx.x;
+  pt.valid = pt.g < ngrids;
+  const int64_t gc = pt.valid ? pt.g : (int64_t)blockIdx.x * TPB;   // clamp to the block's first point
+  pt.px = coords[gc]; pt.py = coords[ngrids + gc]; pt.pz = coords[2 * ngrids + gc];
+  const AtomDev at = atoms[blockIdx.y];
+  const int nlist = cull_images(at, Ls, nimgs, pt.px, pt.py, pt.pz, img_list, red, wcnt);
+  pt.pr = 1.0; pt.pi = 0.0;
+  if (CPLX && periodic) {
+    const double kr = kx * pt.px + ky * pt.py + kz * pt.pz;
+    sincos(-kr, &pt.pi, &pt.pr);
+  }
+  for (int s = at.sh0; s < at.sh1; ++s) {
+    const ShellDev sh = shells[s];
+    switch (sh.l) {
+      case 0: shell_form<0, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      case 1: shell_form<1, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      case 2: shell_form<2, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      default: shell_form<3, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+    }
+  }
+}
+
+__global__ __launch_bounds__(TPB) void eval_ao_kernel(
+    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
+    const double* __restrict__ env, const double* __restrict__ Ls, int nimgs,
+    const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao, int64_t ld) {
+  eval_ao_body<false, false>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, 0});
+}
+
+__global__ __launch_bounds__(TPB) void eval_ao_k_kernel(
+    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
+    const double* __restrict__ env, const double* __restrict__ Ls, const double* __restrict__ phT,
+    int nimgs, double kx, double ky, double kz, int periodic, const double* __restrict__ coords,
+    int64_t ngrids, double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld) {
+  eval_ao_body<true, false>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, 0});
+}
+
+__global__ __launch_bounds__(TPB) void eval_ao_deriv1_kernel(
+    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells, const double* __restrict__ env,
+    const double* __restrict__ Ls, int nimgs, const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao,
+    int64_t ld, int64_t plane) {
+  eval_ao_body<false, true>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, plane});
 }
 
 __global__ __launch_bounds__(TPB) void eval_ao_k_deriv1_kernel(
@@ -560,29 +333,7 @@ __global__ __launch_bounds__(TPB) void eval_ao_k_deriv1_kernel(
     const double* __restrict__ Ls, const double* __restrict__ phT, int nimgs, double kx, double ky, double kz, int periodic,
     const double* __restrict__ coords, int64_t ngrids, double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld,
     int64_t plane) {
-  extern __shared__ int img_list[];
-  __shared__ double red[6][TPB / 64];
-  __shared__ int wcnt[TPB / 64];
-  const int64_t g = (int64_t)blockIdx.x * TPB + threadIdx.x;
-  const bool valid = g < ngrids;
-  const int64_t gc = valid ? g : (int64_t)blockIdx.x * TPB;
-  const double px = coords[gc], py = coords[ngrids + gc], pz = coords[2 * ngrids + gc];
-  const AtomDev at = atoms[blockIdx.y];
-  const int nlist = cull_images(at, Ls, nimgs, px, py, pz, img_list, red, wcnt);
-  double pr = 1.0, pi = 0.0;
-  if (periodic) {
-    const double kr = kx * px + ky * py + kz * pz;
-    sincos(-kr, &pi, &pr);
-  }
-  for (int s = at.sh0; s < at.sh1; ++s) {
-    const ShellDev sh = shells[s];
-    switch (sh.l) {
-      case 0: shell_eval_k_d1_all<0>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, plane, g); break;
-      case 1: shell_eval_k_d1_all<1>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, plane, g); break;
-      case 2: shell_eval_k_d1_all<2>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, plane, g); break;
-      default: shell_eval_k_d1_all<3>(sh, env, Ls, phT, img_list, nlist, px, py, pz, at.x, at.y, at.z, valid, pr, pi, out_re, out_im, ld, plane, g); break;
-    }
-  }
+  eval_ao_body<true, true>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, plane});
 }
 
 __global__ void gather_cols_kernel(const double* __restrict__ src, int64_t ld_src,
@@ -659,38 +410,53 @@ static int upload_ao_tables(isdf_handle h, const int32_t* atm, int natm, const i
   return ISDF_OK;
 }
 
+// The launcher of the four entry points: argument checks, the Bloch factors exp(i k.T) per image (k forms), the tables, the
+// launch.  d_im and kpt are null for the Gamma forms, plane_stride is 0 for the value forms.
+template <bool CPLX, bool D1>
+static int launch_eval_ao(isdf_handle h, const char* label, const int32_t* atm, int natm, const int32_t* bas, int nbas,
+                          const double* env, int nenv, const double* Ls, int nimgs, const double* rcut, const double* kpt,
+                          int periodic_part, const double* d_coords, int64_t ngrids, double* d_re, double* d_im, int64_t ld,
+                          int64_t plane_stride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_coords && d_re && ngrids > 0 && ld >= ngrids);
+  ARG_CHECK(h, !CPLX || (kpt && d_im && Ls && nimgs > 0));
+  std::vector<double> ph(CPLX ? 2 * (size_t)nimgs : 0);
+  for (int i = 0; CPLX && i < nimgs; ++i) {
+    const double kl = kpt[0] * Ls[3 * i] + kpt[1] * Ls[3 * i + 1] + kpt[2] * Ls[3 * i + 2];
+    ph[2 * i] = cos(kl);
+    ph[2 * i + 1] = sin(kl);
+  }
+  AoTables t;
+  int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, CPLX ? ph.data() : nullptr, &t);
+  if (rc) return rc;
+  ARG_CHECK(h, !D1 || plane_stride >= (int64_t)t.nao * ld);
+  dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
+  ProfScope ps(h, label, 8.0 * (CPLX ? 2 : 1) * (D1 ? 4 : 1) * (double)ngrids * t.nao);
+  auto launch = [&](auto kernel, auto... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream, t.d_atoms, t.d_shells, t.d_env, t.d_Ls,
+                       args...);
+  };
+  if constexpr (!CPLX && !D1) launch(eval_ao_kernel, nimgs, d_coords, ngrids, d_re, ld);
+  else if constexpr (!CPLX) launch(eval_ao_deriv1_kernel, nimgs, d_coords, ngrids, d_re, ld, plane_stride);
+  else if constexpr (!D1) launch(eval_ao_k_kernel, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld);
+  else launch(eval_ao_k_deriv1_kernel, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld, plane_stride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
 extern "C" int isdf_eval_ao(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas,
                             const double* env, int nenv, const double* Ls, int nimgs,
                             const double* rcut, const double* d_coords, int64_t ngrids,
                             double* d_ao, int64_t ld) {
-  if (!h) return ISDF_ERR_ARG;
-  ARG_CHECK(h, d_coords && d_ao && ngrids > 0 && ld >= ngrids);
-  AoTables t;
-  int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, &t);
-  if (rc) return rc;
-  dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
-  ProfScope ps(h, "eval_ao_kernel[byte]", 8.0 * (double)ngrids * t.nao);
-  hipLaunchKernelGGL(eval_ao_kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream,
-                     t.d_atoms, t.d_shells, t.d_env, t.d_Ls, nimgs, d_coords, ngrids, d_ao, ld);
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return launch_eval_ao<false, false>(h, "eval_ao_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
+                                      d_coords, ngrids, d_ao, nullptr, ld, 0);
 }
 
 extern "C" int isdf_eval_ao_deriv1(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
                                    int nenv, const double* Ls, int nimgs, const double* rcut, const double* d_coords,
                                    int64_t ngrids, double* d_ao, int64_t ld, int64_t plane_stride) {
-  if (!h) return ISDF_ERR_ARG;
-  ARG_CHECK(h, d_coords && d_ao && ngrids > 0 && ld >= ngrids);
-  AoTables t;
-  int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, &t);
-  if (rc) return rc;
-  ARG_CHECK(h, plane_stride >= (int64_t)t.nao * ld);
-  dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
-  ProfScope ps(h, "eval_ao_deriv1_kernel[byte]", 32.0 * (double)ngrids * t.nao);
-  hipLaunchKernelGGL(eval_ao_deriv1_kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream, t.d_atoms, t.d_shells,
-                     t.d_env, t.d_Ls, nimgs, d_coords, ngrids, d_ao, ld, plane_stride);
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return launch_eval_ao<false, true>(h, "eval_ao_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
+                                     d_coords, ngrids, d_ao, nullptr, ld, plane_stride);
 }
 
 extern "C" int isdf_eval_ao_k(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas,
@@ -698,49 +464,16 @@ extern "C" int isdf_eval_ao_k(isdf_handle h, const int32_t* atm, int natm, const
                               const double* rcut, const double kpt[3], int periodic_part,
                               const double* d_coords, int64_t ngrids, double* d_re, double* d_im,
                               int64_t ld) {
-  if (!h) return ISDF_ERR_ARG;
-  ARG_CHECK(h, kpt && d_coords && d_re && d_im && ngrids > 0 && ld >= ngrids);
-  std::vector<double> ph(2 * (size_t)nimgs);
-  for (int i = 0; i < nimgs; ++i) {
-    const double kl = kpt[0] * Ls[3 * i] + kpt[1] * Ls[3 * i + 1] + kpt[2] * Ls[3 * i + 2];
-    ph[2 * i] = cos(kl);
-    ph[2 * i + 1] = sin(kl);
-  }
-  AoTables t;
-  int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, ph.data(), &t);
-  if (rc) return rc;
-  dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
-  ProfScope ps(h, "eval_ao_k_kernel[byte]", 16.0 * (double)ngrids * t.nao);
-  hipLaunchKernelGGL(eval_ao_k_kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream,
-                     t.d_atoms, t.d_shells, t.d_env, t.d_Ls, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2],
-                     periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld);
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return launch_eval_ao<true, false>(h, "eval_ao_k_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
+                                     periodic_part, d_coords, ngrids, d_re, d_im, ld, 0);
 }
 
 extern "C" int isdf_eval_ao_k_deriv1(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
                                      int nenv, const double* Ls, int nimgs, const double* rcut, const double kpt[3],
                                      int periodic_part, const double* d_coords, int64_t ngrids, double* d_re, double* d_im,
                                      int64_t ld, int64_t plane_stride) {
-  if (!h) return ISDF_ERR_ARG;
-  ARG_CHECK(h, kpt && d_coords && d_re && d_im && ngrids > 0 && ld >= ngrids);
-  std::vector<double> ph(2 * (size_t)nimgs);
-  for (int i = 0; i < nimgs; ++i) {
-    const double kl = kpt[0] * Ls[3 * i] + kpt[1] * Ls[3 * i + 1] + kpt[2] * Ls[3 * i + 2];
-    ph[2 * i] = cos(kl);
-    ph[2 * i + 1] = sin(kl);
-  }
-  AoTables t;
-  int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, ph.data(), &t);
-  if (rc) return rc;
-  ARG_CHECK(h, plane_stride >= (int64_t)t.nao * ld);
-  dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
-  ProfScope ps(h, "eval_ao_k_deriv1_kernel[byte]", 64.0 * (double)ngrids * t.nao);
-  hipLaunchKernelGGL(eval_ao_k_deriv1_kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream, t.d_atoms, t.d_shells,
-                     t.d_env, t.d_Ls, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im,
-                     ld, plane_stride);
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return launch_eval_ao<true, true>(h, "eval_ao_k_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
+                                    periodic_part, d_coords, ngrids, d_re, d_im, ld, plane_stride);
 }
 
 extern "C" int isdf_gather_cols(isdf_handle h, const double* d_src, int nrow, int64_t ld_src,
