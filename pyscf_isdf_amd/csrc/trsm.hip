@@ -351,19 +351,34 @@ int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk
   for (int b = 0; b < nblk; ++b) mmax = std::max(mmax, blk_off_host[b + 1] - blk_off_host[b]);
   const int mpad = (mmax + 31) & ~31;
   ARG_CHECK(h, mmax > 0);
+  // which instantiation runs, under the name rocprofv3 gives it (SQ left out).  Register-resident form for blocks of up to 256
+  // rows (option "block_apply_reg", default on); else 64 columns per workgroup while the block's rows fit 52 KB of LDS (three
+  // workgroups per CU), else 32, else 16
+  const bool reg = h->block_apply_reg && mmax <= 256;
+  const int nt = (mmax + 15) / 16;
+  int tn = 0;
+  const char* label;
+  if (reg) {
+    label = nt <= 8 ? "block_apply_reg_kernel<8,2>[byte]" : nt <= 10 ? "block_apply_reg_kernel<10,2>[byte]"
+          : nt <= 12 ? "block_apply_reg_kernel<12,2>[byte]" : "block_apply_reg_kernel<16,1>[byte]";
+  } else if ((size_t)mpad * (64 + 2) * sizeof(double) <= 52 * 1024) {
+    tn = 64; label = "block_apply_mfma_kernel<64>[byte]";
+  } else if ((size_t)mpad * (32 + 2) * sizeof(double) <= 80 * 1024) {
+    tn = 32; label = "block_apply_mfma_kernel<32>[byte]";
+  } else {
+    ARG_CHECK(h, (size_t)mpad * (16 + 2) * sizeof(double) <= 160 * 1024);
+    tn = 16; label = "block_apply_mfma_kernel<16>[byte]";
+  }
   int32_t* d_off = (int32_t*)isdf_ws(h, "trsm_blk_off", sizeof(int32_t) * (size_t)(nblk + 1));
   if (!d_off) return ISDF_ERR_HIP;
   HIP_TRY(h, hipMemcpyAsync(d_off, blk_off_host, sizeof(int32_t) * (size_t)(nblk + 1), hipMemcpyHostToDevice, h->stream));
-  ProfScope ps(h, "block_apply_mfma_kernel[byte]", 16.0 * (double)blk_off_host[nblk] * (double)n);
-  // register-resident form for blocks of up to 256 rows (option "block_apply_reg", default on)
-  if (h->block_apply_reg && mmax <= 256) {
-    const int nt = (mmax + 15) / 16;
+  ProfScope ps(h, label, 16.0 * (double)blk_off_host[nblk] * (double)n);
+  if (reg) {
     if (nt <= 8) return block_apply_reg_launch<8, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
     if (nt <= 10) return block_apply_reg_launch<10, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
     if (nt <= 12) return block_apply_reg_launch<12, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
     return block_apply_reg_launch<16, 1>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
   }
-  // 64 columns per workgroup while the block's rows fit 52 KB of LDS (three workgroups per CU), else 32, else 16
   // more than 64 KB of dynamic LDS needs the attribute raised once per instantiation (per device: kept in the handle's option map)
 #define ISDF_BA_LAUNCH(TN_, SQ_)                                                                                       \
   do {                                                                                                                 \
@@ -373,12 +388,11 @@ int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk
     hipLaunchKernelGGL(HIP_KERNEL_NAME(block_apply_mfma_kernel<TN_, SQ_>), dim3((unsigned)cdiv(n, TN_), (unsigned)nblk),   \
                        dim3(256), (size_t)mpad * (TN_ + 2) * sizeof(double), h->stream, Dinv, ldd, d_off, X, ldx, n);  \
   } while (0)
-  if ((size_t)mpad * (64 + 2) * sizeof(double) <= 52 * 1024) {
+  if (tn == 64) {
     if (square_input) ISDF_BA_LAUNCH(64, true); else ISDF_BA_LAUNCH(64, false);
-  } else if ((size_t)mpad * (32 + 2) * sizeof(double) <= 80 * 1024) {
+  } else if (tn == 32) {
     if (square_input) ISDF_BA_LAUNCH(32, true); else ISDF_BA_LAUNCH(32, false);
   } else {
-    ARG_CHECK(h, (size_t)mpad * (16 + 2) * sizeof(double) <= 160 * 1024);
     if (square_input) ISDF_BA_LAUNCH(16, true); else ISDF_BA_LAUNCH(16, false);
   }
 #undef ISDF_BA_LAUNCH
