@@ -393,21 +393,27 @@ int isdf_spectral_rows(isdf_handle h, const double* d_in, int nrows, int64_t ld,
  * assembled by an all-to-all before and scattered by another one after this call. */
 int isdf_coulomb_rows(isdf_handle h, const double* d_in, int nrows, int64_t ld,
                       const int32_t mesh[3], const double a[9], int batch, double* d_out, int64_t ldo);
-/* W[q][p] = W[p][q] for q > p. */
+/* W[q][p] = W[p][q] for q > p, in place: the upper triangle and the diagonal are read and stay as they are, whatever the lower
+ * triangle held is overwritten, columns P .. ldw of a row are not touched. */
 int isdf_symmetrize_upper(isdf_handle h, double* d_W, int P, int64_t ldw);
 /* W <- (W + W^T) / 2, or (W - W^T) / 2 with antisymmetric != 0 (the imaginary plane of a Hermitian W^q) (after the two-sided solves of the block-Jacobi route, whose rounding along null(A_PP) is not
- * symmetric; the mean keeps that noise inside null(A_PP) x null(A_PP), mirroring one triangle would not). */
+ * symmetric; the mean keeps that noise inside null(A_PP) x null(A_PP), mirroring one triangle would not).  In place on all P x P
+ * entries, columns P .. ldw not touched; the antisymmetric form leaves an exactly zero diagonal. */
 int isdf_symmetrize_mean(isdf_handle h, double* d_W, int P, int64_t ldw, int antisymmetric);
 
 /* S6. J exactly as pyscf/pbc/df/fft_jk.py:63-107 (Γ, real dm):
  *   rho = sum_mn dm_mn ao_m ao_n;  v = (vol/G) ifft(coulG fft rho).real;  vj = ao (v .* ao)^T.
  * Grid columns [g0, g0+ng) only are contracted when ng < ngrids (grid-sharded partial sums:
  * the density/potential FFT still uses the full grid, so ng<ngrids requires d_vR_in/out staging —
- * see isdf_rho / isdf_vj_from_vR). */
+ * see isdf_rho / isdf_vj_from_vR).  d_vj (nset, nao, nao) is overwritten; the result is bit for bit that of the three pieces
+ * below called in turn on a contiguous density (ldrho = ngrids). */
 int isdf_get_j(isdf_handle h, const double* d_ao, int nao, int64_t ngrids, int64_t ld,
                const int32_t mesh[3], const double a[9],
                const double* d_dm, int nset, double* d_vj);
-/* The three pieces of S6 separately (for grid-sharded multi-GPU runs). */
+/* The three pieces of S6 separately (for grid-sharded multi-GPU runs).  isdf_rho overwrites columns [0, ng) of the nset rows of
+ * d_rho (leading dimension ldrho >= ng, the columns beyond ng are not touched) in passes of 32768 grid columns;
+ * isdf_coulomb_potential convolves nset contiguous rows in place (ldrho == prod(mesh)); isdf_vj_from_vR overwrites d_vj
+ * (nset, nao, nao) with ao (vR[s] .* ao)^T, vR rows of leading dimension ldv >= ng. */
 int isdf_rho(isdf_handle h, const double* d_ao, int nao, int64_t ng, int64_t ld,
              const double* d_dm, int nset, double* d_rho, int64_t ldrho);
 int isdf_coulomb_potential(isdf_handle h, double* d_rho_inout, int nset, int64_t ldrho,
@@ -420,14 +426,18 @@ int isdf_vj_from_vR(isdf_handle h, const double* d_ao, int nao, int64_t ng, int6
  *   vk[i, l] = (vol/G) sum_g [ sum_j ifft(coulG fft(ao_i mo_j))(g) mo_j(g) ] ao_l(g),   mo = C^T ao,
  * d_C (nao, nocc) = occupied MO coefficients times sqrt(occupation).  N*nocc FFT pairs — the cost
  * ISDF removes; provided to MEASURE the fitting error of the ISDF K at full size, not as the fast path.
- * max_rows = pair-density rows convolved per pass (memory: 24 * max_rows * G bytes). */
+ * max_rows = pair-density rows convolved per pass (memory: 24 * max_rows * G bytes; max(1, min(ni, max_rows / nocc)) AO rows per
+ * pass, the last pass ragged).  d_vk is the FULL (nao, nao) matrix: rows [i0, i0 + ni) are OVERWRITTEN, every other row is left as
+ * it is, ni = 0 writes nothing.  (The k-point form below differs on both counts: an (ni, nao) block, accumulated into.) */
 int isdf_get_k_exact(isdf_handle h, const double* d_ao, int nao, int64_t ngrids, int64_t ld,
                      const double* d_C, int nocc, const int32_t mesh[3], const double a[9],
                      int i0, int ni, int max_rows, double* d_vk);
 
 /* S7. K from the interpolation factorisation:
  *   vk = aoP^T [ (aoP dm aoP^T) .* W ] aoP   for rows [row0,row0+nrows) of the Hadamard matrix
- * (row-sharded partial sums for multi-GPU; pass row0=0,nrows=P for the whole thing). */
+ * (row-sharded partial sums for multi-GPU; pass row0=0,nrows=P for the whole thing).  d_vk (nset, nao, nao) is OVERWRITTEN as a
+ * whole by every call - the caller adds the partial sums of its windows - and nrows = 0 gives exact zeros.  The Hadamard rows are
+ * walked in passes of 4096; d_W is read on rows [row0, row0 + nrows), columns [0, P) only and need not be symmetric. */
 int isdf_get_k(isdf_handle h, const double* d_aoP, int P, int nao,
                const double* d_W, int64_t ldw, int row0, int nrows,
                const double* d_dm, int nset, double* d_vk);
@@ -449,16 +459,20 @@ int isdf_coulG_q(isdf_handle h, const int32_t mesh[3], const double a[9], const 
  *                     d_coulG = the G real values of get_coulG(cell, q) (pbc/tools/pbc.py:230-420) in
  *                     fftfreq order; complex transform (Z2Z) because coulG(q+G) is not inversion
  *                     symmetric.  Real and imaginary parts in d_Wre / d_Wim; upper_only as in isdf_coulomb_W.
- *   isdf_symmetrize_hermitian:  M[q][p] = conj(M[p][q]) for q > p.
+ *   isdf_symmetrize_hermitian:  M[q][p] = conj(M[p][q]) for q > p: the lower triangles of both planes are overwritten, upper triangles
+ *                     and diagonals stay as they are - the diagonal of d_Wim is NOT zeroed, a Hermitian result needs it zero on entry.
  *   (isdf_W_from_factor is applied to both planes.)
  *   isdf_finish_Wq:   d_Wc (P, P) complex interleaved = (Wre + i Wim)[p][q] * ph[p] * conj(ph[q]),
- *                     d_phase = (P, 2) with ph[p] = exp(-i q.r_p).
+ *                     d_phase = (P, 2) with ph[p] = exp(-i q.r_p) (any complex numbers: no unit modulus is assumed); d_Wc is
+ *                     contiguous (leading dimension P) and overwritten, d_Wre / d_Wim (leading dimension ldw) are not modified.
  *   isdf_get_k_pair:  d_vk (nao, nao) complex += scale * A1^H [ (A2 D2 A2^H) .* Wq ] A1 with
  *                     A1, A2 = phi^{k1}, phi^{k2} at the interpolation points, (P, nao) complex interleaved,
- *                     D2 (nao, nao) complex; rocBLAS zgemm + a fused complex Hadamard kernel.
+ *                     D2 (nao, nao) complex, Wq (P, P) complex interleaved, none of them assumed Hermitian; d_vk is ACCUMULATED into;
+ *                     rocBLAS zgemm + a fused complex Hadamard kernel.
  *   isdf_rho_k:       d_rho[g] += scale * sum_ij D_ij u_i(g) conj(u_j(g)) (real part; Hermitian D), with
- *                     d_DTr/d_DTi = real/imag planes of D^T (fft_jk.py:84-88).
- *   isdf_vj_k:        vj_ij = sum_g conj(u_i(g)) vR[g] u_j(g)  (fft_jk.py:100-107), planes re/im. */
+ *                     d_DTr/d_DTi = real/imag planes of D^T (fft_jk.py:84-88); d_rho (ng, one row) is ACCUMULATED into, in passes
+ *                     of 32768 grid columns.
+ *   isdf_vj_k:        vj_ij = sum_g conj(u_i(g)) vR[g] u_j(g)  (fft_jk.py:100-107), planes re/im (nao, nao), overwritten. */
 int isdf_coulomb_Wq(isdf_handle h, const double* d_theta, int P, int64_t ldt, const int32_t mesh[3],
                     const double* d_coulG, double weight, int row0, int nrows, int batch,
                     int upper_only, double* d_Wre, double* d_Wim, int64_t ldw);
@@ -474,7 +488,8 @@ int isdf_get_k_pair(isdf_handle h, const double* d_A1, const double* d_A2, const
  *   vk[p - i0, k'] += weight sum_g { sum_j conv_q[conj(u1_p) m2_j](g) conj(m2_j(g)) } u1_k'(g),   p in [i0, i0 + ni)
  * d_u1r/d_u1i (nao, ld1): periodic parts of the Bloch AOs at k1 (isdf_eval_ao_k, periodic_part = 1); d_m2r/d_m2i (nocc, ld2):
  * those of the occupied orbitals at k2 scaled with sqrt(occ); d_coulG (G): isdf_coulG_q of q = k2 - k1; max_rows: FFT rows per
- * pass (>= nocc); d_vk_re/d_vk_im (ni, nao) row-major are ACCUMULATED into (the caller sums over k2). */
+ * pass (>= nocc; max(1, min(ni, max_rows / nocc)) AO rows per pass, the last pass ragged); d_vk_re/d_vk_im (ni, nao) row-major -
+ * row 0 is AO row i0 - are ACCUMULATED into (the caller sums over k2); ni = 0 touches nothing.  hipFFT Z2Z on every mesh. */
 int isdf_get_k_exact_kpt(isdf_handle h, const double* d_u1r, const double* d_u1i, int nao, int64_t ld1,
                          const double* d_m2r, const double* d_m2i, int nocc, int64_t ld2, const int32_t mesh[3],
                          const double* d_coulG, double weight, int i0, int ni, int max_rows, double* d_vk_re,
@@ -484,7 +499,8 @@ int isdf_get_k_exact_kpt(isdf_handle h, const double* d_u1r, const double* d_u1i
  * isdf_gemm_nt on the real / imaginary planes.
  *   isdf_coulomb_rows_q:   (d_re + i d_im)[r] = ifft(coulG(q) fft(rows[r])) for nrows real rows of G = prod(mesh) points (ld == G);
  *                          d_coulG from isdf_coulG_q; the convolution step of isdf_coulomb_Wq on its own
- *   isdf_zhadamard_planes: (Ar + i Ai) .*= (Br + i Bi) on `rows` x `cols` planes */
+ *   isdf_zhadamard_planes: (Ar + i Ai) .*= (Br + i Bi) on `rows` x `cols` planes (rows <= 65535, more is ISDF_ERR_ARG; columns
+ *                          cols .. lda are not touched) */
 int isdf_coulomb_rows_q(isdf_handle h, const double* d_rows, int nrows, int64_t ld, const int32_t mesh[3],
                         const double* d_coulG, double* d_re, double* d_im);
 /* (d_re + i d_im)[r] (mesh[a] x mesh[b] entries, the two axes other than `axis`, C order) = the 3-D DFT of the real row r on the
@@ -548,7 +564,7 @@ int isdf_rowdot3(isdf_handle h, int M, int64_t K, double alpha, const double* d_
  *   isdf_gemm_nn:       C (M, ldc) = alpha A (M, K; lda) B (K, N; ldb) + beta C, row-major, N contiguous (rocBLAS dgemm; with
  *                       option "gemm_nn_own" the own MFMA NN kernel for alpha = 1, beta = 0 on aligned operands with
  *                       K % 32 == 0 and full 256-row tiles)
- *   isdf_hadamard_rows: X (rows, ldx) .*= Y (rows, ldy) on `cols` columns */
+ *   isdf_hadamard_rows: X (rows, ldx) .*= Y (rows, ldy) on `cols` columns (rows <= 65535, more is ISDF_ERR_ARG) */
 int isdf_gemm_nn(isdf_handle h, int M, int64_t N, int K, double alpha, const double* d_A, int64_t lda, const double* d_B,
                  int64_t ldb, double beta, double* d_C, int64_t ldc);
 int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const double* d_Y, int64_t ldy, int rows, int64_t cols);
@@ -560,7 +576,8 @@ int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const double* d_
  *   isdf_uniform_grid:          coords (3, G) of the uniform grid of ``mesh`` in cell.get_uniform_grids' order and folding
  *                               (pyscf/pbc/gto/cell.py:874-898, wrap_around = True), structure of arrays, on the device
  *   isdf_rho_pair:              rho[i, g] = sum_(mu<nA, nu<nB) aoA[mu, g] dm[i, mu, nu] aoB[nu, g]   (both AO blocks with leading
- *                               dimension ld; the rectangular form of isdf_rho: dense x (dense + sparse) pairs of a level)
+ *                               dimension ld; the rectangular form of isdf_rho: dense x (dense + sparse) pairs of a level);
+ *                               overwrites columns [0, ng) of the rows of d_rho (ldrho >= ng) in passes of 32768 grid columns
  *   isdf_mg_embed_density:      spec[set] (+)= scale * fft(field[set] on mesh_sub) written at the matching frequencies of the
  *                               dense mesh (multigrid.py:665-673: tools.fft, weight, _takebak_4d); accumulate = 0 overwrites
  *                               the touched entries only - zero the spectrum first unless mesh_sub == mesh

@@ -390,7 +390,8 @@ def test_get_j_matches_fftdf_pin(be):
 
 
 def test_get_k(be):
-    """S7 vs the oracle on random W (symmetric) and dm; also a row-sharded partial sum."""
+    """S7 vs the oracle on random W (symmetric) and dm; also a row-sharded partial sum.  (More than one Hadamard pass, windows past
+    row 0, ldw > P and a non-symmetric W: test_gpu_jk_sweep.py::test_B_get_k_windows.)"""
     rng = np.random.default_rng(2)
     P, nao = 300, 17
     aoP = rng.standard_normal((P, nao))
@@ -813,6 +814,7 @@ def test_ao_eri_and_ao2mo_from_the_factorisation():
 
 
 def test_symmetrize_mean_and_probe_rows(be):
+    # every ragged tile edge, ldw > P and the padding: test_gpu_jk_sweep.py::test_D_symmetrize_mean
     rng = np.random.default_rng(3)
     for P in (1, 31, 70):                                         # ragged 32 x 32 tiles
         M = rng.standard_normal((P, P))
