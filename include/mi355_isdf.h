@@ -125,6 +125,15 @@ int isdf_eval_ao(isdf_handle h,
 int isdf_eval_ao_deriv1(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
                         int nenv, const double* Ls, int nimgs, const double* rcut, const double* d_coords,
                         int64_t ngrids, double* d_ao, int64_t ld, int64_t plane_stride);
+/* The same with the Cartesian second derivatives (numint.eval_ao(deriv=2)): ten planes in its order - value, x, y, z, xx, xy, xz,
+ * yy, yz, zz - at d_ao + comp * plane_stride; planes 0..3 are those of isdf_eval_ao_deriv1 bit for bit (the same pass of the same
+ * shell body), planes 4..9 come from two more passes over the image list, three components each:
+ *   d_a d_b phi = (d_a d_b ang) R - 2 [d_b d_a ang + d_a d_b ang + delta_ab ang] R1 + 4 d_a d_b ang R2,  R_n = sum_p c_p a_p^n exp(-a_p r^2),
+ * d = r - R_atom - T.  For the exact nuclear derivative of a GGA energy (pyscf/pbc/grad/krks.py:91 takes ao_deriv = 2).  Gamma
+ * point only. */
+int isdf_eval_ao_deriv2(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
+                        int nenv, const double* Ls, int nimgs, const double* rcut, const double* d_coords,
+                        int64_t ngrids, double* d_ao, int64_t ld, int64_t plane_stride);
 /* k-point form: Bloch sums of values and Cartesian derivatives (times exp(-i k.r) with periodic_part - the derivative stays that
  * of the Bloch function), real and imaginary planes d_re / d_im + comp * plane_stride. */
 int isdf_eval_ao_k_deriv1(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
@@ -548,7 +557,14 @@ int isdf_pp_projector_overlaps(isdf_handle h, const int32_t* atm, int natm, cons
  * isdf_rowdot3:  d_out[x * ldo + m] (+)= alpha sum_k A_x[m, k] s[k] B[m, k], x = 0, 1, 2, A_x = d_A + x astride (M, lda), B (M, ldb),
  *     K contiguous; accumulate = 0 overwrites.  The contraction of a local potential's Pulay force: A_x the three grad phi planes
  *     of isdf_eval_ao_deriv1, s the potential, B = D phi.  One workgroup per row, 16-byte loads when every base is 16-byte
- *     aligned and lda, ldb, astride are even, scalar loads otherwise; fixed summation order. */
+ *     aligned and lda, ldb, astride are even, scalar loads otherwise; fixed summation order.
+ * isdf_gga_aow:  the weighted AO planes of a GGA potential's Pulay force, from the ten planes of isdf_eval_ao_deriv2 (M rows, K
+ *     columns, leading dimension ld, plane stride plane) and four weight rows d_w + c ldw = (v_rho, w_x, w_y, w_z) of length K:
+ *       Z[m, k]   = v_rho[k] phi[m, k] + sum_y w_y[k] d_y phi[m, k]          (d_Z, M x K, ldz)
+ *       G_x[m, k] = sum_y w_y[k] d_x d_y phi[m, k],  x = 0, 1, 2            (d_G + x gstride, M x K, ldg)
+ *     ("aow" of pyscf/grad/rks.py:228 and _make_dR_dao_w of rks.py:196 without its wv[0] part).  One streaming launch: 10 planes
+ *     read, 4 written; two columns per lane by 16-byte accesses when every base is 16-byte aligned and every stride even, one
+ *     column per lane otherwise; padding columns are neither read nor written. */
 int isdf_pp_local_force(isdf_handle h, const double* d_rho, int nset, int64_t ldrho, int natm, const double* coords,
                         const double* pp_par, const int32_t mesh[3], const double a[9], double* d_out);
 int isdf_pp_projector_overlaps_ip(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas,
@@ -557,6 +573,8 @@ int isdf_pp_projector_overlaps_ip(isdf_handle h, const int32_t* atm, int natm, c
                                   const int32_t mesh[3], const double a[9], double* d_out);
 int isdf_rowdot3(isdf_handle h, int M, int64_t K, double alpha, const double* d_A, int64_t lda, int64_t astride, const double* d_s,
                  const double* d_B, int64_t ldb, int accumulate, double* d_out, int64_t ldo);
+int isdf_gga_aow(isdf_handle h, int M, int64_t K, const double* d_ao, int64_t ld, int64_t plane, const double* d_w, int64_t ldw,
+                 double* d_Z, int64_t ldz, double* d_G, int64_t ldg, int64_t gstride);
 
 /* Robust-fitting K (Dunlap's correction on top of the ISDF exchange).  With V_P = conv(Theta_P) kept
  * on the device, per batch of points:  F (nb, G) = (phi_P D)(nb, N) . phi (N, G)  [isdf_gemm_nn],  F .*= V rows

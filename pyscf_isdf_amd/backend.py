@@ -166,6 +166,14 @@ class HipBackend:
         assert coords_soa.is_contiguous() and ao4.dim() == 3 and ao4.shape[0] == 4 and ao4.stride(2) == 1 and ao4.shape[2] >= G
         self.handle.call('isdf_eval_ao_deriv1', *tables, self._p(coords_soa), G, self._p(ao4), ao4.stride(1), ao4.stride(0))
 
+    def eval_ao_deriv2(self, atm, bas, env, Ls, rcut, coords_soa, ao10):
+        """ao10 (10, nao, ld) <- values, x, y, z and xx, xy, xz, yy, yz, zz derivatives on coords_soa (3, G)."""
+        self._stream()
+        tables = self._ao_tables(atm, bas, env, Ls, rcut)
+        G = coords_soa.shape[1]
+        assert coords_soa.is_contiguous() and ao10.dim() == 3 and ao10.shape[0] == 10 and ao10.stride(2) == 1 and ao10.shape[2] >= G
+        self.handle.call('isdf_eval_ao_deriv2', *tables, self._p(coords_soa), G, self._p(ao10), ao10.stride(1), ao10.stride(0))
+
     def eval_ao_k(self, atm, bas, env, Ls, rcut, kpt, periodic_part, coords_soa, out_re, out_im):
         self._stream()
         tables = self._ao_tables(atm, bas, env, Ls, rcut)
@@ -836,6 +844,16 @@ class HipBackend:
         assert tuple(out.shape) == (3, M) and out.stride(1) == 1
         self.handle.call('isdf_rowdot3', M, K, float(alpha), self._p(A3), A3.stride(1), A3.stride(0), self._p(s), self._p(B),
                          B.stride(0), int(bool(accumulate)), self._p(out), out.stride(0))
+
+    def gga_aow(self, ao10, wv, Z, G3):
+        """Z[m, k] = wv[0, k] phi[m, k] + sum_y wv[1 + y, k] d_y phi[m, k] and G3[x, m, k] = sum_y wv[1 + y, k] d_x d_y phi[m, k] from
+        the ten planes ao10 (10, M, K) of eval_ao_deriv2; wv (4, K), Z (M, K), G3 (3, M, K), K contiguous."""
+        self._stream()
+        _, M, K = ao10.shape
+        assert ao10.shape[0] == 10 and ao10.stride(2) == 1 and tuple(wv.shape) == (4, K) and wv.stride(1) == 1
+        assert tuple(Z.shape) == (M, K) and Z.stride(1) == 1 and tuple(G3.shape) == (3, M, K) and G3.stride(2) == 1
+        self.handle.call('isdf_gga_aow', M, K, self._p(ao10), ao10.stride(1), ao10.stride(0), self._p(wv), wv.stride(0), self._p(Z),
+                         Z.stride(0), self._p(G3), G3.stride(1), G3.stride(0))
 
     def _pp_overlaps(self, entry, atm, bas, env, coords, kpt, proj_tab, proj_rl, mesh, a, out):
         self._stream()

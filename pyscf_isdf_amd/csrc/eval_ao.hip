@@ -1,5 +1,6 @@
 // S1: periodic AO collocation on gfx950 (real spherical GTOs, l <= 3): values and Cartesian first derivatives, at the Γ point
-// or as Bloch sums at a k-point.  Four kernels, one body (eval_ao_body -> cull_images, shell_eval).
+// or as Bloch sums at a k-point, and the Γ-point second derivatives.  Five kernels, one body (eval_ao_body -> cull_images,
+// shell_eval).
 //
 // One workgroup = 256 consecutive grid points x one atom.  The workgroup first culls the lattice
 // translations against the bounding box of its points (LDS list), then every lane walks only the
@@ -93,6 +94,40 @@ __device__ inline void angular_grad(const double* __restrict__ d, double* __rest
   }
 }
 
+// Cartesian second derivatives hang[m][h] of the same polynomials, h = xx, xy, xz, yy, yz, zz: zero for s and p, constants for d,
+// linear for f
+template <int L>
+__device__ inline void angular_hess(const double* __restrict__ d, double (*hang)[6]) {
+  constexpr int DEG = 2 * L + 1;
+#pragma unroll
+  for (int m = 0; m < DEG; ++m)
+#pragma unroll
+    for (int h = 0; h < 6; ++h) hang[m][h] = 0.0;
+  if (L == 2) {
+    hang[0][1] = D_XY;
+    hang[1][4] = D_XY;
+    hang[2][0] = -2.0 * D_Z2_XXYY;  hang[2][3] = -2.0 * D_Z2_XXYY;  hang[2][5] = 2.0 * D_Z2_ZZ;
+    hang[3][2] = D_XY;
+    hang[4][0] = 2.0 * D_X2Y2;      hang[4][3] = -2.0 * D_X2Y2;
+  } else if (L == 3) {
+    const double dx = d[0], dy = d[1], dz = d[2];
+    hang[0][0] = 6.0 * F_3 * dy;    hang[0][1] = 6.0 * F_3 * dx;    hang[0][3] = -6.0 * F_3 * dy;
+    hang[1][1] = F_2M * dz;         hang[1][2] = F_2M * dy;         hang[1][4] = F_2M * dx;
+    hang[2][0] = -2.0 * F_1 * dy;   hang[2][1] = -2.0 * F_1 * dx;   hang[2][3] = -6.0 * F_1 * dy;
+    hang[2][4] = 8.0 * F_1 * dz;    hang[2][5] = 8.0 * F_1 * dy;
+    hang[3][0] = -6.0 * F_0 * dz;   hang[3][2] = -6.0 * F_0 * dx;   hang[3][3] = -6.0 * F_0 * dz;
+    hang[3][4] = -6.0 * F_0 * dy;   hang[3][5] = 12.0 * F_0 * dz;
+    hang[4][0] = -6.0 * F_1 * dx;   hang[4][1] = -2.0 * F_1 * dy;   hang[4][2] = 8.0 * F_1 * dz;
+    hang[4][3] = -2.0 * F_1 * dx;   hang[4][5] = 8.0 * F_1 * dx;
+    hang[5][0] = 2.0 * F_2 * dz;    hang[5][2] = 2.0 * F_2 * dx;    hang[5][3] = -2.0 * F_2 * dz;   hang[5][4] = -2.0 * F_2 * dy;
+    hang[6][0] = 6.0 * F_3 * dx;    hang[6][1] = -6.0 * F_3 * dy;   hang[6][3] = -6.0 * F_3 * dx;
+  }
+}
+
+// the Cartesian pair (a, b) of second-derivative component 4 + h, in the order xx, xy, xz, yy, yz, zz of numint.eval_ao(deriv=2)
+__device__ constexpr int hess_a(int h) { return h < 3 ? 0 : (h < 5 ? 1 : 2); }
+__device__ constexpr int hess_b(int h) { return h < 3 ? h : (h < 5 ? h - 2 : 2); }
+
 __device__ inline double wave_min(double v) {
   for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
   return v;
@@ -167,9 +202,11 @@ struct Out {
   __device__ Out from(int x) const { return Out{re + x * plane, im + x * plane, ld, plane}; }
 };
 
-// One shell on the workgroup's image list: components X0 .. X0 + NX - 1 (0 the value, 1..3 d/dx, d/dy, d/dz) of
-//   phi = fac ang(d) R(r^2), R = sum_p c_p exp(-a_p r^2);  grad phi = grad(ang) R - 2 d ang R1, R1 = sum_p c_p a_p exp(-a_p r^2)
-// (numint.eval_ao(deriv=1), pyscf/lib/gto/deriv1.c:60-69 for the radial part), summed over the images - plainly (Gamma) or, CPLX,
+// One shell on the workgroup's image list: components X0 .. X0 + NX - 1 (0 the value, 1..3 d/dx, d/dy, d/dz, 4..9 the second
+// derivatives xx, xy, xz, yy, yz, zz) of
+//   phi = fac ang(d) R(r^2), R = sum_p c_p exp(-a_p r^2);  grad phi = grad(ang) R - 2 d ang R1, R1 = sum_p c_p a_p exp(-a_p r^2);
+//   d_a d_b phi = (d_a d_b ang) R - 2 [d_b d_a ang + d_a d_b ang + delta_ab ang] R1 + 4 d_a d_b ang R2, R2 = sum_p c_p a_p^2 exp(-a_p r^2)
+// (numint.eval_ao(deriv=1 / 2), pyscf/lib/gto/deriv1.c:60-69 for the radial part), summed over the images - plainly (Gamma) or, CPLX,
 // with the Bloch factor exp(i k.T) of the table phT and multiplied at the store by the point's exp(-i k.r): the lattice-periodic
 // part u^k = exp(-i k.r) phi^k, or phi^k itself when that factor is 1.  A derivative is then that of the Bloch function times the
 // phase, NOT the derivative of the periodic part - callers that differentiate pair products conj(u_i) u_j never see the
@@ -180,6 +217,7 @@ __device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const dou
                                   const Out out) {
   constexpr int DEG = 2 * L + 1;
   constexpr bool D1 = X0 + NX > 1;       // a derivative component is among them: rad1 and the angular gradients are needed
+  constexpr bool D2 = X0 + NX > 4;       // a second derivative: rad2 and the angular second derivatives too
   double accr[NX][NCMAX][DEG], acci[CPLX ? NX : 1][NCMAX][DEG];
 #pragma unroll
   for (int x = 0; x < NX; ++x)
@@ -200,9 +238,9 @@ __device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const dou
     if (rr < sh.rcut2) {
       double tr = 1.0, ti = 0.0;
       if (CPLX) { tr = phT[2 * iL]; ti = phT[2 * iL + 1]; }
-      double rad[NCMAX], rad1[NCMAX];
+      double rad[NCMAX], rad1[NCMAX], rad2[NCMAX];
 #pragma unroll
-      for (int c = 0; c < NCMAX; ++c) { rad[c] = 0.0; rad1[c] = 0.0; }
+      for (int c = 0; c < NCMAX; ++c) { rad[c] = 0.0; rad1[c] = 0.0; rad2[c] = 0.0; }
       for (int p = 0; p < sh.nprim; ++p) {
         const double e = exp(-es[p] * rr) * fac;
 #pragma unroll
@@ -210,11 +248,13 @@ __device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const dou
           if (c < sh.nctr) {
             rad[c] += cs[c * sh.nprim + p] * e;
             if (D1) rad1[c] += cs[c * sh.nprim + p] * es[p] * e;
+            if (D2) rad2[c] += cs[c * sh.nprim + p] * es[p] * es[p] * e;
           }
       }
-      double ang[DEG], gang[DEG][3];
+      double ang[DEG], gang[DEG][3], hang[DEG][6];
       if (D1) angular_grad<L>(d, ang, gang);
       else angular<L>(d[0], d[1], d[2], ang);
+      if (D2) angular_hess<L>(d, hang);
       // every accumulator has its own sum, so the order of these three loops changes no bit; m, c, x is the one measured: with the
       // component innermost under c, m the Gamma gradient pass takes 24 more VGPRs, with it outermost it runs 0.8 % slower
 #pragma unroll
@@ -223,8 +263,15 @@ __device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const dou
         for (int c = 0; c < NCMAX; ++c)
 #pragma unroll
           for (int x = 0; x < NX; ++x) {
-            const int k = X0 + x > 0 ? X0 + x - 1 : 0;       // Cartesian direction of a derivative component
-            const double v = (X0 + x == 0) ? rad[c] * ang[m] : gang[m][k] * rad[c] - 2.0 * d[k] * ang[m] * rad1[c];
+            double v;
+            if (X0 + x < 4) {
+              const int k = X0 + x > 0 ? X0 + x - 1 : 0;     // Cartesian direction of a derivative component
+              v = (X0 + x == 0) ? rad[c] * ang[m] : gang[m][k] * rad[c] - 2.0 * d[k] * ang[m] * rad1[c];
+            } else {
+              const int h = X0 + x - 4, a = hess_a(h), b = hess_b(h);
+              v = hang[m][h] * rad[c] - 2.0 * (d[b] * gang[m][a] + d[a] * gang[m][b] + (a == b ? ang[m] : 0.0)) * rad1[c] +
+                  4.0 * d[a] * d[b] * ang[m] * rad2[c];
+            }
             if (CPLX) {
               accr[x][c][m] += v * tr;
               acci[x][c][m] += v * ti;
@@ -254,17 +301,23 @@ __device__ inline void shell_eval(const ShellDev sh, const AtomDev at, const dou
   }
 }
 
-// the instantiations of a form: values in one pass; Gamma gradients all four components in one pass; Bloch gradients one
-// component per pass, which keeps the complex accumulators in registers
-template <int L, bool CPLX, bool D1>
+// the instantiations of a form (DERIV = highest derivative): values in one pass; Gamma gradients all four components in one pass;
+// Bloch gradients one component per pass, which keeps the complex accumulators in registers; Gamma second derivatives (DERIV = 2)
+// the gradient pass and then xx, xy, xz and yy, yz, zz in a pass each (three components x NCMAX x 7 accumulators of an f shell)
+template <int L, bool CPLX, int DERIV>
 __device__ inline void shell_form(const ShellDev sh, const AtomDev at, const double* __restrict__ env, const double* __restrict__ Ls,
                                   const double* __restrict__ phT, const int* __restrict__ img_list, int nlist, const Point pt,
                                   const Out out) {
-  if constexpr (!D1) {
+  if constexpr (DERIV == 0) {
     shell_eval<L, CPLX, 0, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
   } else if constexpr (!CPLX) {
     shell_eval<L, false, 0, 4>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
+    if constexpr (DERIV == 2) {
+      shell_eval<L, false, 4, 3>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(4));
+      shell_eval<L, false, 7, 3>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(7));
+    }
   } else {
+    static_assert(DERIV == 1, "no Bloch second derivatives");
     shell_eval<L, true, 0, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out);
     shell_eval<L, true, 1, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(1));
     shell_eval<L, true, 2, 1>(sh, at, env, Ls, phT, img_list, nlist, pt, out.from(2));
@@ -272,10 +325,11 @@ __device__ inline void shell_form(const ShellDev sh, const AtomDev at, const dou
   }
 }
 
-// The body of the four kernels: one workgroup = 256 consecutive grid points x one atom.  Load the point, cull the images against
+// The body of the five kernels: one workgroup = 256 consecutive grid points x one atom.  Load the point, cull the images against
 // the workgroup's box, take the point's phase, then walk the atom's shells.  Output AO-major: (nao, ld) planes, four of them
-// (value, d/dx, d/dy, d/dz) at stride out.plane for the derivative forms, a real and an imaginary set for the k forms.
-template <bool CPLX, bool D1>
+// (value, d/dx, d/dy, d/dz) at stride out.plane for the derivative forms - ten with the second derivatives - a real and an
+// imaginary set for the k forms.
+template <bool CPLX, int DERIV>
 __device__ __forceinline__ void eval_ao_body(const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
                                              const double* __restrict__ env, const double* __restrict__ Ls,
                                              const double* __restrict__ phT, int nimgs, double kx, double ky, double kz, int periodic,
@@ -298,10 +352,10 @@ __device__ __forceinline__ void eval_ao_body(const AtomDev* __restrict__ atoms, 
   for (int s = at.sh0; s < at.sh1; ++s) {
     const ShellDev sh = shells[s];
     switch (sh.l) {
-      case 0: shell_form<0, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
-      case 1: shell_form<1, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
-      case 2: shell_form<2, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
-      default: shell_form<3, CPLX, D1>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      case 0: shell_form<0, CPLX, DERIV>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      case 1: shell_form<1, CPLX, DERIV>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      case 2: shell_form<2, CPLX, DERIV>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
+      default: shell_form<3, CPLX, DERIV>(sh, at, env, Ls, phT, img_list, nlist, pt, out); break;
     }
   }
 }
@@ -310,7 +364,7 @@ __global__ __launch_bounds__(TPB) void eval_ao_kernel(
     const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells,
     const double* __restrict__ env, const double* __restrict__ Ls, int nimgs,
     const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao, int64_t ld) {
-  eval_ao_body<false, false>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, 0});
+  eval_ao_body<false, 0>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, 0});
 }
 
 __global__ __launch_bounds__(TPB) void eval_ao_k_kernel(
@@ -318,14 +372,21 @@ __global__ __launch_bounds__(TPB) void eval_ao_k_kernel(
     const double* __restrict__ env, const double* __restrict__ Ls, const double* __restrict__ phT,
     int nimgs, double kx, double ky, double kz, int periodic, const double* __restrict__ coords,
     int64_t ngrids, double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld) {
-  eval_ao_body<true, false>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, 0});
+  eval_ao_body<true, 0>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, 0});
 }
 
 __global__ __launch_bounds__(TPB) void eval_ao_deriv1_kernel(
     const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells, const double* __restrict__ env,
     const double* __restrict__ Ls, int nimgs, const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao,
     int64_t ld, int64_t plane) {
-  eval_ao_body<false, true>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, plane});
+  eval_ao_body<false, 1>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, plane});
+}
+
+__global__ __launch_bounds__(TPB) void eval_ao_deriv2_kernel(
+    const AtomDev* __restrict__ atoms, const ShellDev* __restrict__ shells, const double* __restrict__ env,
+    const double* __restrict__ Ls, int nimgs, const double* __restrict__ coords, int64_t ngrids, double* __restrict__ ao,
+    int64_t ld, int64_t plane) {
+  eval_ao_body<false, 2>(atoms, shells, env, Ls, nullptr, nimgs, 0.0, 0.0, 0.0, 0, coords, ngrids, Out{ao, nullptr, ld, plane});
 }
 
 __global__ __launch_bounds__(TPB) void eval_ao_k_deriv1_kernel(
@@ -333,7 +394,7 @@ __global__ __launch_bounds__(TPB) void eval_ao_k_deriv1_kernel(
     const double* __restrict__ Ls, const double* __restrict__ phT, int nimgs, double kx, double ky, double kz, int periodic,
     const double* __restrict__ coords, int64_t ngrids, double* __restrict__ out_re, double* __restrict__ out_im, int64_t ld,
     int64_t plane) {
-  eval_ao_body<true, true>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, plane});
+  eval_ao_body<true, 1>(atoms, shells, env, Ls, phT, nimgs, kx, ky, kz, periodic, coords, ngrids, Out{out_re, out_im, ld, plane});
 }
 
 __global__ void gather_cols_kernel(const double* __restrict__ src, int64_t ld_src,
@@ -410,9 +471,9 @@ static int upload_ao_tables(isdf_handle h, const int32_t* atm, int natm, const i
   return ISDF_OK;
 }
 
-// The launcher of the four entry points: argument checks, the Bloch factors exp(i k.T) per image (k forms), the tables, the
-// launch.  d_im and kpt are null for the Gamma forms, plane_stride is 0 for the value forms.
-template <bool CPLX, bool D1>
+// The launcher of the five entry points: argument checks, the Bloch factors exp(i k.T) per image (k forms), the tables, the
+// launch.  d_im and kpt are null for the Gamma forms, plane_stride is 0 for the value forms.  DERIV = highest derivative.
+template <bool CPLX, int DERIV>
 static int launch_eval_ao(isdf_handle h, const char* label, const int32_t* atm, int natm, const int32_t* bas, int nbas,
                           const double* env, int nenv, const double* Ls, int nimgs, const double* rcut, const double* kpt,
                           int periodic_part, const double* d_coords, int64_t ngrids, double* d_re, double* d_im, int64_t ld,
@@ -429,16 +490,17 @@ static int launch_eval_ao(isdf_handle h, const char* label, const int32_t* atm, 
   AoTables t;
   int rc = upload_ao_tables(h, atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, CPLX ? ph.data() : nullptr, &t);
   if (rc) return rc;
-  ARG_CHECK(h, !D1 || plane_stride >= (int64_t)t.nao * ld);
+  ARG_CHECK(h, DERIV == 0 || plane_stride >= (int64_t)t.nao * ld);
   dim3 grid((unsigned)cdiv(ngrids, TPB), (unsigned)natm);
-  ProfScope ps(h, label, 8.0 * (CPLX ? 2 : 1) * (D1 ? 4 : 1) * (double)ngrids * t.nao);
+  ProfScope ps(h, label, 8.0 * (CPLX ? 2 : 1) * (DERIV == 2 ? 10 : DERIV == 1 ? 4 : 1) * (double)ngrids * t.nao);
   auto launch = [&](auto kernel, auto... args) {
     hipLaunchKernelGGL(kernel, grid, dim3(TPB), (size_t)nimgs * sizeof(int), h->stream, t.d_atoms, t.d_shells, t.d_env, t.d_Ls,
                        args...);
   };
-  if constexpr (!CPLX && !D1) launch(eval_ao_kernel, nimgs, d_coords, ngrids, d_re, ld);
-  else if constexpr (!CPLX) launch(eval_ao_deriv1_kernel, nimgs, d_coords, ngrids, d_re, ld, plane_stride);
-  else if constexpr (!D1) launch(eval_ao_k_kernel, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld);
+  if constexpr (!CPLX && DERIV == 0) launch(eval_ao_kernel, nimgs, d_coords, ngrids, d_re, ld);
+  else if constexpr (!CPLX && DERIV == 1) launch(eval_ao_deriv1_kernel, nimgs, d_coords, ngrids, d_re, ld, plane_stride);
+  else if constexpr (!CPLX) launch(eval_ao_deriv2_kernel, nimgs, d_coords, ngrids, d_re, ld, plane_stride);
+  else if constexpr (DERIV == 0) launch(eval_ao_k_kernel, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld);
   else launch(eval_ao_k_deriv1_kernel, t.d_phT, nimgs, kpt[0], kpt[1], kpt[2], periodic_part ? 1 : 0, d_coords, ngrids, d_re, d_im, ld, plane_stride);
   KERNEL_CHECK(h);
   return ISDF_OK;
@@ -448,15 +510,22 @@ extern "C" int isdf_eval_ao(isdf_handle h, const int32_t* atm, int natm, const i
                             const double* env, int nenv, const double* Ls, int nimgs,
                             const double* rcut, const double* d_coords, int64_t ngrids,
                             double* d_ao, int64_t ld) {
-  return launch_eval_ao<false, false>(h, "eval_ao_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
+  return launch_eval_ao<false, 0>(h, "eval_ao_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
                                       d_coords, ngrids, d_ao, nullptr, ld, 0);
 }
 
 extern "C" int isdf_eval_ao_deriv1(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
                                    int nenv, const double* Ls, int nimgs, const double* rcut, const double* d_coords,
                                    int64_t ngrids, double* d_ao, int64_t ld, int64_t plane_stride) {
-  return launch_eval_ao<false, true>(h, "eval_ao_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
+  return launch_eval_ao<false, 1>(h, "eval_ao_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
                                      d_coords, ngrids, d_ao, nullptr, ld, plane_stride);
+}
+
+extern "C" int isdf_eval_ao_deriv2(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas, const double* env,
+                                   int nenv, const double* Ls, int nimgs, const double* rcut, const double* d_coords,
+                                   int64_t ngrids, double* d_ao, int64_t ld, int64_t plane_stride) {
+  return launch_eval_ao<false, 2>(h, "eval_ao_deriv2_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, nullptr, 0,
+                                  d_coords, ngrids, d_ao, nullptr, ld, plane_stride);
 }
 
 extern "C" int isdf_eval_ao_k(isdf_handle h, const int32_t* atm, int natm, const int32_t* bas, int nbas,
@@ -464,7 +533,7 @@ extern "C" int isdf_eval_ao_k(isdf_handle h, const int32_t* atm, int natm, const
                               const double* rcut, const double kpt[3], int periodic_part,
                               const double* d_coords, int64_t ngrids, double* d_re, double* d_im,
                               int64_t ld) {
-  return launch_eval_ao<true, false>(h, "eval_ao_k_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
+  return launch_eval_ao<true, 0>(h, "eval_ao_k_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
                                      periodic_part, d_coords, ngrids, d_re, d_im, ld, 0);
 }
 
@@ -472,7 +541,7 @@ extern "C" int isdf_eval_ao_k_deriv1(isdf_handle h, const int32_t* atm, int natm
                                      int nenv, const double* Ls, int nimgs, const double* rcut, const double kpt[3],
                                      int periodic_part, const double* d_coords, int64_t ngrids, double* d_re, double* d_im,
                                      int64_t ld, int64_t plane_stride) {
-  return launch_eval_ao<true, true>(h, "eval_ao_k_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
+  return launch_eval_ao<true, 1>(h, "eval_ao_k_deriv1_kernel[byte]", atm, natm, bas, nbas, env, nenv, Ls, nimgs, rcut, kpt,
                                     periodic_part, d_coords, ngrids, d_re, d_im, ld, plane_stride);
 }
 

@@ -273,6 +273,70 @@ extern "C" int isdf_rowdot3(isdf_handle h, int M, int64_t K, double alpha, const
   return ISDF_OK;
 }
 
+// ---- the weighted AO planes of a GGA potential's Pulay force ------------------------------------------------
+namespace {
+constexpr int AOW_TPB = 256;
+
+struct Aow4 { double z, g0, g1, g2; };
+// p: the ten values (value, x, y, z, xx, xy, xz, yy, yz, zz) of one AO at one point; v, wx, wy, wz the point's weights
+__device__ inline Aow4 aow_point(const double* p, double v, double wx, double wy, double wz) {
+  return Aow4{v * p[0] + wx * p[1] + wy * p[2] + wz * p[3], wx * p[4] + wy * p[5] + wz * p[6], wx * p[5] + wy * p[7] + wz * p[8],
+              wx * p[6] + wy * p[8] + wz * p[9]};
+}
+
+// grid (column blocks, rows): Z[m, k] = v phi + w . grad phi, G_x[m, k] = sum_y w_y d_x d_y phi.  VEC: two columns per lane by 16-byte
+// loads and stores (every base 16-byte aligned, every stride even), the odd last column by the scalar form; else one column per lane.
+template <bool VEC>
+__global__ __launch_bounds__(AOW_TPB) void gga_aow_kernel(int64_t K, const double* __restrict__ ao, int64_t ld, int64_t plane,
+                                                          const double* __restrict__ w, int64_t ldw, double* __restrict__ Z,
+                                                          int64_t ldz, double* __restrict__ G, int64_t ldg, int64_t gstride) {
+  const int64_t m = blockIdx.y;
+  const int64_t k = ((int64_t)blockIdx.x * AOW_TPB + threadIdx.x) * (VEC ? 2 : 1);
+  if (k >= K) return;
+  const double* a = ao + m * ld + k;
+  double* z = Z + m * ldz + k;
+  double* g = G + m * ldg + k;
+  if (VEC && k + 1 < K) {
+    double p0[10], p1[10];
+#pragma unroll
+    for (int c = 0; c < 10; ++c) {
+      const double2 t = *(const double2*)(a + c * plane);
+      p0[c] = t.x; p1[c] = t.y;
+    }
+    const double2 v = *(const double2*)(w + k), wx = *(const double2*)(w + ldw + k), wy = *(const double2*)(w + 2 * ldw + k),
+                  wz = *(const double2*)(w + 3 * ldw + k);
+    const Aow4 r0 = aow_point(p0, v.x, wx.x, wy.x, wz.x), r1 = aow_point(p1, v.y, wx.y, wy.y, wz.y);
+    *(double2*)z = make_double2(r0.z, r1.z);
+    *(double2*)g = make_double2(r0.g0, r1.g0);
+    *(double2*)(g + gstride) = make_double2(r0.g1, r1.g1);
+    *(double2*)(g + 2 * gstride) = make_double2(r0.g2, r1.g2);
+  } else {
+    double p[10];
+#pragma unroll
+    for (int c = 0; c < 10; ++c) p[c] = a[c * plane];
+    const Aow4 r = aow_point(p, w[k], w[ldw + k], w[2 * ldw + k], w[3 * ldw + k]);
+    z[0] = r.z; g[0] = r.g0; g[gstride] = r.g1; g[2 * gstride] = r.g2;
+  }
+}
+}  // namespace
+
+extern "C" int isdf_gga_aow(isdf_handle h, int M, int64_t K, const double* d_ao, int64_t ld, int64_t plane, const double* d_w,
+                            int64_t ldw, double* d_Z, int64_t ldz, double* d_G, int64_t ldg, int64_t gstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_ao && d_w && d_Z && d_G && M > 0 && M <= 65535 && K > 0);
+  ARG_CHECK(h, ld >= K && ldw >= K && ldz >= K && ldg >= K && plane >= (int64_t)(M - 1) * ld + K && gstride >= (int64_t)(M - 1) * ldg + K);
+  const bool vec = ((((uintptr_t)d_ao | (uintptr_t)d_w | (uintptr_t)d_Z | (uintptr_t)d_G) & 15) == 0) &&
+                   ((ld | plane | ldw | ldz | ldg | gstride) & 1) == 0;
+  ProfScope ps(h, vec ? "gga_aow_kernel<true>[byte]" : "gga_aow_kernel<false>[byte]", 8.0 * (14.0 * (double)M + 4.0) * (double)K);
+  const dim3 grid((unsigned)cdiv(K, AOW_TPB * (vec ? 2 : 1)), (unsigned)M);
+  if (vec)
+    hipLaunchKernelGGL(gga_aow_kernel<true>, grid, dim3(AOW_TPB), 0, h->stream, K, d_ao, ld, plane, d_w, ldw, d_Z, ldz, d_G, ldg, gstride);
+  else
+    hipLaunchKernelGGL(gga_aow_kernel<false>, grid, dim3(AOW_TPB), 0, h->stream, K, d_ao, ld, plane, d_w, ldw, d_Z, ldz, d_G, ldg, gstride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
 extern "C" int isdf_gemm_nn(isdf_handle h, int M, int64_t N, int K, double alpha, const double* d_A, int64_t lda,
                             const double* d_B, int64_t ldb, double beta, double* d_C, int64_t ldc) {
   if (!h) return ISDF_ERR_ARG;

@@ -116,13 +116,14 @@ class JKE1Mixin:
         be.gemm_nn(self.aoP, D.T.contiguous(), left)
         return left, self.ao
 
-    def _e1_chunks(self, ncomp=4):
-        """(s0, s1, collocation (4, nao, n) of (phi, grad phi), or phi (nao, n) for ncomp = 1) over the grid in chunks of
-        e1_grid_chunk columns; the same shells, images and cutoffs as collocate().  One buffer: a chunk is valid until the next."""
+    def _e1_chunks(self, ncomp=4, chunk=None):
+        """(s0, s1, collocation (4, nao, n) of (phi, grad phi), phi (nao, n) for ncomp = 1, or (10, nao, n) with the second
+        derivatives for ncomp = 10) over the grid in chunks of e1_grid_chunk columns (or ``chunk``); the same shells, images and
+        cutoffs as collocate().  One buffer: a chunk is valid until the next."""
         cell, be = self.cell, self.backend
         nao = cell.nao_nr()
         G = int(np.prod(self.mesh))
-        chunk = max(1, min(int(self.e1_grid_chunk), G))
+        chunk = max(1, min(int(self.e1_grid_chunk if chunk is None else chunk), G))
         rcut = gto.estimate_rcut_per_shell(cell)
         Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
         ao_args = (np.asarray(cell._atm), np.asarray(cell._bas), np.asarray(cell._env), Ls, rcut)
@@ -134,6 +135,9 @@ class JKE1Mixin:
             if ncomp == 1:
                 out = buf[:nao * (s1 - s0)].view(nao, s1 - s0)
                 be.eval_ao(*ao_args, xyz, out)
+            elif ncomp == 10:
+                out = buf[:10 * nao * (s1 - s0)].view(10, nao, s1 - s0)
+                be.eval_ao_deriv2(*ao_args, xyz, out)
             else:
                 out = buf[:4 * nao * (s1 - s0)].view(4, nao, s1 - s0)
                 be.eval_ao_deriv1(*ao_args, xyz, out)

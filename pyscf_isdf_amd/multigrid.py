@@ -27,7 +27,7 @@ scatters the small level matrices into J on the host.
 
 Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, hybrid_coeff, nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc,
 cache_xc_kernel1, _gen_rhf_response, _gen_uhf_response, multi_grids_tasks, multigrid_fftdf - the names of
-pyscf/pbc/dft/multigrid/__init__.py and multigrid.py.
+pyscf/pbc/dft/multigrid/__init__.py and multigrid.py - and the XC nuclear forces get_vxc_e1, xc_nuc_grad, xc_nuc_grad_uks (xc_grad.py).
 
 K is the ISDF exchange of the parent class (``MultiGridFFTDF(ISDF)``): hybrid functionals get J/XC from here and K from the
 interpolation, which is the pairing SURVEY section 8 f-3 names.  XC: the Slater exchange ('lda,') and Becke's 1988 exchange
@@ -644,6 +644,31 @@ def nr_uks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=Fa
     return _nr_ks(mydf, fn, isinstance(xc_code, (tuple, list)), dm_in, kpts, kpts_band, with_j, return_j, True)
 
 
+def _xc_dispatch(be, fn, raw, spin):
+    """Which kernels evaluate the functional ``fn`` (a row of _XC_TABLE; ``raw``: caller's weights) - shared by _nr_ks and the
+    nuclear forces of xc_grad: (ncomp, pair_lyp, per_channel, channel).  ncomp: 1 without gradients, 4 with; channel(rho (ncomp, G),
+    exc (G,), vxc (ncomp, G)) launches the one kernel of a density - isdf_lda_exchange [+ isdf_lda_vwn_add], isdf_gga_b88 for Becke's
+    exchange alone, isdf_xc_fused for every other weighted sum; ``spin``: the channel is the exchange part alone (at 2 rho_s), pair_lyp
+    says that LYP of (rho_a, rho_b) together follows (isdf_gga_lyp_polarised), per_channel that there is a channel part at all."""
+    cs, cb, cv, fit, cl, _ = fn
+    ncomp = 4 if (cb != 0 or cl != 0 or raw) else 1
+    pair_lyp = spin and cl != 0                                              # LYP of (rho_a, rho_b) together
+    if spin:
+        cv, cl = 0.0, 0.0                                                    # per channel: the exchange part alone
+    per_channel = not (pair_lyp and cs == 0 and cb == 0)                     # ',lyp' of a pair: nothing but the coupled term
+
+    def channel(rho, exc, vxc):
+        if ncomp == 1:
+            be.lda_exchange(rho[0], exc, vxc[0])
+            if cv != 0:
+                be.lda_vwn_add(rho[0], exc, vxc[0])
+        elif (cs, cb, cv, cl) == (0.0, 1.0, 0.0, 0.0) and not raw:
+            be.gga_b88(rho[0], rho[1:], exc, vxc[0], vxc[1:])
+        else:
+            be.xc_fused(rho[0], rho[1:], (cs, cb, cv, cl), fit == 'RPA', exc, vxc[0], vxc[1:])
+    return ncomp, pair_lyp, per_channel, channel
+
+
 def _nr_ks(mydf, fn, raw, dm, kpts, kpts_band, with_j, return_j, spin):
     """The Kohn-Sham pass pair behind nr_rks and nr_uks: rho (and grad rho for a GGA, real-space gradients per level) from the
     ladder, the functional ``fn`` (a row of _XC_TABLE) on the dense mesh, the potential v_rho phi phi + (de/d grad rho) .
@@ -653,11 +678,7 @@ def _nr_ks(mydf, fn, raw, dm, kpts, kpts_band, with_j, return_j, spin):
     exchange at (2 rho_s, 2 grad rho_s) - potentials come out as they are, energies halved - LYP couples the channels and comes
     from isdf_gga_lyp_polarised on (rho_a, rho_b), its energy added once; the Hartree potential is that of the total density."""
     be, cell = mydf.backend, mydf.cell
-    cs, cb, cv, fit, cl, _ = fn
-    ncomp = 4 if (cb != 0 or cl != 0 or raw) else 1
-    pair_lyp = spin and cl != 0                                              # LYP of (rho_a, rho_b) together
-    if spin:
-        cv, cl = 0.0, 0.0                                                    # per channel: the exchange part alone
+    ncomp, pair_lyp, per_channel, channel = _xc_dispatch(be, fn, raw, spin)
     dms, kpts, band, shape = mydf._format_dms(dm, kpts, kpts_band)
     # the XC functional sees the real density: the Hermitian part of D (the reference takes the real part of rho)
     spec = mydf._eval_rhoG(mydf._hermitian_parts(dms, anti=False)[0][1], kpts, ncomp)
@@ -676,18 +697,9 @@ def _nr_ks(mydf, fn, raw, dm, kpts, kpts_band, with_j, return_j, spin):
     exc = be.empty((nset, G))
     vxc = be.empty((ncomp, nset, G))                                         # v_rho and, for a GGA, de/d grad rho
     nelec, excsum, ecoul = np.zeros(nset), np.zeros(nset), np.zeros(nset)
-    per_channel = not (pair_lyp and cs == 0 and cb == 0)                     # ',lyp' of a pair: nothing but the coupled term
     for i in range(nset):
-        if not per_channel:
-            pass
-        elif ncomp == 1:
-            be.lda_exchange(rho[0, i], exc[i], vxc[0, i])
-            if cv != 0:
-                be.lda_vwn_add(rho[0, i], exc[i], vxc[0, i])
-        elif (cs, cb, cv, cl) == (0.0, 1.0, 0.0, 0.0) and not raw:
-            be.gga_b88(rho[0, i], rho[1:, i], exc[i], vxc[0, i], vxc[1:, i])
-        else:
-            be.xc_fused(rho[0, i], rho[1:, i], (cs, cb, cv, cl), fit == 'RPA', exc[i], vxc[0, i], vxc[1:, i])
+        if per_channel:
+            channel(rho[:, i], exc[i], vxc[:, i])
         nelec[i] = be.dot(rho[0, i]) / scale * weight
         if per_channel:
             excsum[i] = be.dot(rho[0, i], exc[i]) / scale * weight
@@ -1049,3 +1061,6 @@ def multigrid_fftdf(mf):
 
 
 multigrid = multigrid_fftdf
+
+
+from .xc_grad import get_vxc_e1, xc_nuc_grad, xc_nuc_grad_uks      # noqa: E402,F401  (the XC nuclear forces; xc_grad.py)

@@ -84,8 +84,9 @@ class PPGradMixin:
     def nuc_grad_local(self, vR, dm, kpts=None):
         """The Pulay force of a real local potential on the dense mesh, (natm, 3) or (nset, natm, 3) for a stack:
             - 2 sum_(mu in a) sum_nu D^sym_(mu nu) w sum_g d_x phi_mu(g) v(g) phi_nu(g),   w = vol / G.
-        vR is (G,) shared by the densities or (nset, G), one per density, on the host or the device: the XC potential of nr_rks,
-        for instance.  Only the symmetric part of dm contributes."""
+        vR is (G,) shared by the densities or (nset, G), one per density, on the host or the device: the XC potential of an LDA
+        code, for instance (a GGA's force needs the gradient terms too: multigrid.xc_nuc_grad).  Only the symmetric part of dm
+        contributes."""
         self._ppg_refuse(kpts, 'nuc_grad_local')
         dms, single = self._ppg_dms(dm)
         be = self.backend
