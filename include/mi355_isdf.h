@@ -698,6 +698,19 @@ int isdf_gemm_nt_had3(isdf_handle h, int M, int N, int64_t K, double alpha, cons
                       int64_t ldh, const double* d_B, int64_t ldb, int64_t bstride, double beta, double* d_C, int64_t ldc,
                       int64_t cstride);
 
+/* Hadamard NN product, the hot loop of the contracted exchange force get_k_nuc_grad:
+ *   C (M, ldc) = alpha sum_k A[m,k] H[k,n] B[k,n] + beta C,   A (M, K; lda) with K contiguous, H (K, N; ldh) and B (K, N; ldb) with
+ * N contiguous.  B is not modified, H o B is never stored, beta = 0 does not read C.  ONE launch: the own NN kernel (256 x 128
+ * tile over the whole K, no slabs, no atomics: repeatable bits) with H loaded at B's coordinates and multiplied into the B staging
+ * registers, alpha and beta in its epilogue, for ANY M >= 1 (rows are clamped on load and bounded on store; the full-tile rule
+ * of isdf_gemm_nn does not apply).  That kernel takes K % 32 == 0, N even, even lda / ldh / ldb and 16-byte aligned A, H, B; ldc
+ * and the base of C are free.  The rest runs the composition inside this entry point: a copy of B times H in the workspace
+ * (isdf_hadamard_rows), then isdf_gemm_nn.  A general K is SPLIT: the K % 32 last rows are composed first (with the caller's
+ * beta), then the kernel accumulates the largest multiple-of-32 prefix onto them (K < 32: the composition alone).  An odd N or
+ * leading dimension or an unaligned base composes the whole K.  d_H may not be NULL. */
+int isdf_gemm_nn_had(isdf_handle h, int M, int64_t N, int K, double alpha, const double* d_A, int64_t lda, const double* d_H,
+                     int64_t ldh, const double* d_B, int64_t ldb, double beta, double* d_C, int64_t ldc);
+
 #ifdef __cplusplus
 }
 #endif

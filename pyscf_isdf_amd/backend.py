@@ -556,6 +556,17 @@ class HipBackend:
                          H.stride(0) if H is not None else 0, self._p(B3), B3.stride(1), B3.stride(0), float(beta), self._p(C3),
                          C3.stride(1), C3.stride(0))
 
+    def gemm_nn_had(self, A, H, B, C, alpha=1.0, beta=0.0):
+        """C (M, N) = alpha A (M, K) (H .* B) (K, N) + beta C in one launch, row-major; B is not modified and H .* B is never stored
+        (include/mi355_isdf.h isdf_gemm_nn_had)."""
+        self._stream()
+        M, K = A.shape
+        N = B.shape[1]
+        assert tuple(B.shape) == (K, N) and tuple(H.shape) == (K, N) and tuple(C.shape) == (M, N)
+        assert A.stride(1) == 1 and H.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1
+        self.handle.call('isdf_gemm_nn_had', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(H), H.stride(0), self._p(B),
+                         B.stride(0), float(beta), self._p(C), C.stride(0))
+
     # ---- k-point M^q from the packed half spectra of the fit rows (DESIGN.md section 6b) ------------------------------------
     def pack_table_pm(self, table, mesh, idx, scale, s, a):
         """s, a (ldx,) <- scale (c(G_t) +- (m_t - 1) c(-G_t)) on the packed points idx (int32 half-spectrum indices), each value on

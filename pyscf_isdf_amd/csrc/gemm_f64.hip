@@ -25,6 +25,8 @@
 //    Algorithmic work: 2*M*N*K flop; bound: FP64 MFMA (78.6 TF/s).
 //  * gemm_nt_had3: C_a += alpha (A o H) B_a^T for three B_a in one launch (the exchange derivative's T_a): variant D with the
 //    factor H multiplied into the A operand registers and a 128 x 32 tile of all three components per unit.
+//  * gemm_nn_had: C = alpha A (H o B) + beta C (the contracted exchange force's Z): the NN form's unit body with the factor H
+//    multiplied into the B staging registers, alpha and beta in the epilogue, any M >= 1 (waves past the row edge only stage).
 //  * Every kernel finds its unit with xcd_unit / decode_tile / slab_range (the NN form: decode_supertile) and stores its
 //    accumulators with ISDF_STORE_ACC.  Variant B's unit body, tile_256x128, is a function template that leaves the tile in
 //    accumulator registers: gemm_nt_mfma_kernel_b and the Gram triangles are that body between two ways of finding a unit
@@ -742,6 +744,8 @@ struct GemmNNArgs {
   int M, N, K;                   // K % 32 == 0, N even
   int ntm, ntn, stm, stn, ngm;   // tiles, super-tile shape, super-tiles along M
   int64_t nunits, nunits_pad;
+  const double* H; int64_t ldh;  // gemm_nn_had_kernel only: the Hadamard factor on B, and the epilogue's factors
+  double alpha, beta;
 };
 
 // super-tiles M-fastest, tiles M-fastest inside one; the tiles of a ragged super-tile past the edge do not exist
@@ -752,8 +756,11 @@ __device__ __forceinline__ Tile decode_supertile(int64_t unit, const GemmNNArgs&
   return {(int)(grp % g.ngm) * g.stm + within % g.stm, (int)(grp / g.ngm) * g.stn + within / g.stm, 0};
 }
 
-template <bool SQ>
-__global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
+// The unit body of both NN kernels.  HAD: the Hadamard factor H (K x N, as B) is loaded at B's coordinates with B's edge clamping
+// and multiplied into the B staging registers on their way to LDS (H o B is never stored, B is not modified), the six global
+// loads per chunk become eight, and the epilogue applies alpha and beta (beta = 0 does not read C).
+template <bool SQ, bool HAD>
+__device__ __forceinline__ void nn_unit(const GemmNNArgs& g) {
   extern __shared__ double smem[];                      // [2][BM2*LDT] A | [2][BK*LDN] B
   double* sA = smem;
   double* sB = smem + 2 * BM2 * LDT;
@@ -779,9 +786,13 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
   const double* pB0 = g.B + (int64_t)krow * g.ldb + min(tn * BN + 2 * nseg, g.N - 2);
   const double* pB1 = pB0 + 8 * g.ldb;
   const int64_t bstep = (int64_t)BK * g.ldb;
+  const double* pH0 = HAD ? g.H + (int64_t)krow * g.ldh + min(tn * BN + 2 * nseg, g.N - 2) : nullptr;
+  const double* pH1 = HAD ? pH0 + 8 * g.ldh : nullptr;
+  const int64_t hstep = HAD ? (int64_t)BK * g.ldh : 0;
 
   double2 xa0, xa1, xa2, xa3, xb0, xb1, ya0, ya1, ya2, ya3, yb0, yb1;
-#define ISDF_NN_LOAD(C, A0, A1, A2, A3, B0, B1)                                               \
+  double2 xh0, xh1, yh0, yh1;                           // HAD only
+#define ISDF_NN_LOAD(C, A0, A1, A2, A3, B0, B1, H0, H1)                                       \
   {                                                                                           \
     const int off = (C) * BK;                                                                 \
     const int64_t offb = (C) * bstep;                                                         \
@@ -791,12 +802,17 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
     A3 = *reinterpret_cast<const double2*>(pA3 + off);                                        \
     B0 = *reinterpret_cast<const double2*>(pB0 + offb);                                       \
     B1 = *reinterpret_cast<const double2*>(pB1 + offb);                                       \
+    if (HAD) {                                                                                \
+      H0 = *reinterpret_cast<const double2*>(pH0 + (C) * hstep);                              \
+      H1 = *reinterpret_cast<const double2*>(pH1 + (C) * hstep);                              \
+    }                                                                                         \
   }
 #define ISDF_NN_ST1(P, R) { double* q_ = (P); q_[0] = R.x; q_[1] = R.y; }
-#define ISDF_NN_STORE(BUF, A0, A1, A2, A3, B0, B1)                                            \
+#define ISDF_NN_STORE(BUF, A0, A1, A2, A3, B0, B1, H0, H1)                                    \
   {                                                                                           \
     double* qa = sA + (BUF) * BM2 * LDT + srow * LDT + sseg * 2;                              \
     double* qb = sB + (BUF) * BK * LDN + krow * LDN + 2 * nseg;                               \
+    if (HAD) { B0.x *= H0.x; B0.y *= H0.y; B1.x *= H1.x; B1.y *= H1.y; }                      \
     ISDF_NN_ST1(qa, A0) ISDF_NN_ST1(qa + 64 * LDT, A1) ISDF_NN_ST1(qa + 128 * LDT, A2)        \
     ISDF_NN_ST1(qa + 192 * LDT, A3)                                                           \
     *reinterpret_cast<double2*>(qb) = B0;                                                     \
@@ -826,7 +842,7 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
     ISDF_NN_FRAG(BUF, 1, a1, b1)                                                              \
     LOAD_AHEAD                                                                                \
     ISDF_MFMA16(a0, b0)                                                                       \
-    ISDF_ISSUE(0x020, 6)                                                                      \
+    ISDF_ISSUE(0x020, HAD ? 8 : 6)                                                            \
     __builtin_amdgcn_sched_barrier(0);                                                        \
     ISDF_NN_FRAG(BUF, 2, a0, b0)                                                              \
     ISDF_MFMA16(a1, b1)                                                                       \
@@ -844,24 +860,55 @@ __global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) {
     __builtin_amdgcn_sched_barrier(0);                                                        \
   }
 
-  ISDF_NN_LOAD(0, xa0, xa1, xa2, xa3, xb0, xb1)
-  ISDF_NN_LOAD(1, ya0, ya1, ya2, ya3, yb0, yb1)
-  ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1)
+  ISDF_NN_LOAD(0, xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1)
+  ISDF_NN_LOAD(1, ya0, ya1, ya2, ya3, yb0, yb1, yh0, yh1)
+  ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1)
   __syncthreads();
   ISDF_NN_FRAG(0, 0, a0, b0)
   __builtin_amdgcn_sched_barrier(0);
-  for (int c = 0; c < nchunks; c += 2) {
-    ISDF_NN_CHUNK(0, ISDF_NN_LOAD(min(c + 2, last), xa0, xa1, xa2, xa3, xb0, xb1), ISDF_NN_STORE(1, ya0, ya1, ya2, ya3, yb0, yb1))
-    ISDF_NN_CHUNK(1, ISDF_NN_LOAD(min(c + 3, last), ya0, ya1, ya2, ya3, yb0, yb1), ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1))
+  // HAD takes any M: a wave whose 64 rows all lie past the edge (M = r of an SCF density is often 32 - 128) only stages its share of
+  // the operands and meets the barriers - one per chunk, as the waves that compute - so that the live waves have their SIMD's
+  // MFMA pipe to themselves.  The condition is uniform over a wave; without HAD it is constant and the loop is the one loop.
+  if (!HAD || tm * BM2 + wm * 64 < g.M) {
+    for (int c = 0; c < nchunks; c += 2) {
+      ISDF_NN_CHUNK(0, ISDF_NN_LOAD(min(c + 2, last), xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1),
+                    ISDF_NN_STORE(1, ya0, ya1, ya2, ya3, yb0, yb1, yh0, yh1))
+      ISDF_NN_CHUNK(1, ISDF_NN_LOAD(min(c + 3, last), ya0, ya1, ya2, ya3, yb0, yb1, yh0, yh1),
+                    ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1))
+    }
+  } else {
+    for (int c = 0; c < nchunks; c += 2) {
+      ISDF_NN_LOAD(min(c + 2, last), xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1)
+      ISDF_NN_STORE(1, ya0, ya1, ya2, ya3, yb0, yb1, yh0, yh1)
+      __syncthreads();
+      ISDF_NN_LOAD(min(c + 3, last), ya0, ya1, ya2, ya3, yb0, yb1, yh0, yh1)
+      ISDF_NN_STORE(0, xa0, xa1, xa2, xa3, xb0, xb1, xh0, xh1)
+      __syncthreads();
+    }
+    return;
   }
-  ISDF_STORE_ACC(4, 4, tm * BM2 + wm * 64, tn * BN + wn * 64, g.M, g.N,
-                 { const double v = acc[i][j][r]; g.C[(int64_t)row * g.ldc + col] = SQ ? v * v : v; })
+  if (HAD) {
+    ISDF_STORE_ACC(4, 4, tm * BM2 + wm * 64, tn * BN + wn * 64, g.M, g.N, {
+      double* q = g.C + (int64_t)row * g.ldc + col;
+      const double v = acc[i][j][r];
+      *q = (g.beta == 0.0) ? g.alpha * v : g.alpha * v + g.beta * (*q);
+    })
+  } else {
+    ISDF_STORE_ACC(4, 4, tm * BM2 + wm * 64, tn * BN + wn * 64, g.M, g.N,
+                   { const double v = acc[i][j][r]; g.C[(int64_t)row * g.ldc + col] = SQ ? v * v : v; })
+  }
 #undef ISDF_NN_LOAD
 #undef ISDF_NN_ST1
 #undef ISDF_NN_STORE
 #undef ISDF_NN_FRAG
 #undef ISDF_NN_CHUNK
 }
+
+template <bool SQ>
+__global__ __launch_bounds__(TPB2, 2) void gemm_nn_mfma_kernel(GemmNNArgs g) { nn_unit<SQ, false>(g); }
+
+// C = alpha A (H o B) + beta C: the Z of the contracted exchange force
+__global__ __launch_bounds__(TPB2, 2) void gemm_nn_had_kernel(GemmNNArgs g) { nn_unit<false, true>(g); }
 #undef ISDF_MFMA16
 #undef ISDF_ISSUE
 
@@ -1267,9 +1314,9 @@ bool gemm_nn_f64_supported(isdf_handle h, int64_t M, int64_t N, int64_t K, const
          rows_aligned16(A, lda) && rows_aligned16(B, ldb) && M < 2147483647LL && N < 2147483647LL && K < 2147483647LL;
 }
 
-int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
-                double* C, int64_t ldc, bool square) {
-  ARG_CHECK(h, A && B && C && lda >= K && ldb >= N && ldc >= N && gemm_nn_f64_supported(h, M, N, K, A, lda, B, ldb));
+// tiles and super-tiles of the NN kernels for an M x N output
+static GemmNNArgs nn_args(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
+                          int64_t ldc) {
   GemmNNArgs g;
   g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
   g.M = (int)M; g.N = (int)N; g.K = (int)K;
@@ -1279,12 +1326,59 @@ int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A,
   g.ngm = (int)cdiv(g.ntm, g.stm);
   g.nunits = (int64_t)g.ngm * cdiv(g.ntn, g.stn) * 32;
   g.nunits_pad = cdiv(g.nunits, 8) * 8;
+  g.H = nullptr; g.ldh = 0; g.alpha = 1.0; g.beta = 0.0;
+  return g;
+}
+
+int gemm_nn_f64(isdf_handle h, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb,
+                double* C, int64_t ldc, bool square) {
+  ARG_CHECK(h, A && B && C && lda >= K && ldb >= N && ldc >= N && gemm_nn_f64_supported(h, M, N, K, A, lda, B, ldb));
+  const GemmNNArgs g = nn_args(M, N, K, A, lda, B, ldb, C, ldc);
   ARG_CHECK(h, g.nunits_pad < 2147483647LL);
   const size_t lds = sizeof(double) * 2 * (BM2 * LDT + BK * LDN);
   if (int rc = raise_lds_once(h, h->attr_gemm_nn, lds, gemm_nn_mfma_kernel<true>, gemm_nn_mfma_kernel<false>)) return rc;
   ProfScope ps(h, square ? "gemm_nn_mfma_kernel<true>[flop]" : "gemm_nn_mfma_kernel<false>[flop]", 2.0 * M * N * (double)K);
   if (square) hipLaunchKernelGGL(gemm_nn_mfma_kernel<true>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
   else hipLaunchKernelGGL(gemm_nn_mfma_kernel<false>, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+// Exposed as isdf_gemm_nn_had (declared in include/mi355_isdf.h).
+extern "C" int isdf_gemm_nn_had(isdf_handle h, int M, int64_t N, int K, double alpha, const double* d_A, int64_t lda,
+                                const double* d_H, int64_t ldh, const double* d_B, int64_t ldb, double beta, double* d_C,
+                                int64_t ldc) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, M > 0 && N > 0 && K > 0 && d_A && d_H && d_B && d_C && lda >= K && ldh >= N && ldb >= N && ldc >= N);
+  const bool aligned = N % 2 == 0 && N < 2147483647LL && rows_aligned16(d_A, lda) && rows_aligned16(d_H, ldh) && rows_aligned16(d_B, ldb);
+  // the kernel takes the largest multiple-of-32 prefix of K; the K tail, or the whole K of operands it does not fit (an odd N or
+  // leading dimension, an unaligned base), goes through the composition: a copy of B times H, then the NN product
+  const int Kf = aligned ? K - K % 32 : 0, Kt = K - Kf;
+  if (Kt) {
+    const double* Bt = d_B + (int64_t)Kf * ldb;
+    const double* Ht = d_H + (int64_t)Kf * ldh;
+    double* HB = (double*)isdf_ws(h, "nn_had_HB", sizeof(double) * (size_t)Kt * (size_t)N);
+    if (!HB) return ISDF_ERR_HIP;
+    HIP_TRY(h, hipMemcpy2DAsync(HB, sizeof(double) * (size_t)N, Bt, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)N,
+                                (size_t)Kt, hipMemcpyDeviceToDevice, h->stream));
+    for (int r0 = 0; r0 < Kt; r0 += 32768) {
+      const int nr = Kt - r0 < 32768 ? Kt - r0 : 32768;
+      if (int rc = isdf_hadamard_rows(h, HB + (int64_t)r0 * N, N, Ht + (int64_t)r0 * ldh, ldh, nr, N)) return rc;
+    }
+    // the tail first, with the caller's beta; the prefix then accumulates onto it
+    if (int rc = isdf_gemm_nn(h, M, N, Kt, alpha, d_A + Kf, lda, HB, N, beta, d_C, ldc)) return rc;
+    if (!Kf) return ISDF_OK;
+    beta = 1.0;
+  }
+  // any M >= 1: the kernel clamps the rows it loads and bounds the rows it stores
+  K = Kf;
+  GemmNNArgs g = nn_args(M, N, K, d_A, lda, d_B, ldb, d_C, ldc);
+  ARG_CHECK(h, g.nunits_pad < 2147483647LL);
+  g.H = d_H; g.ldh = ldh; g.alpha = alpha; g.beta = beta;
+  const size_t lds = sizeof(double) * 2 * (BM2 * LDT + BK * LDN);
+  if (int rc = raise_lds_once(h, h->attr_gemm_nn_had, lds, gemm_nn_had_kernel)) return rc;
+  ProfScope ps(h, "gemm_nn_had_kernel[flop]", 2.0 * M * N * (double)K);
+  hipLaunchKernelGGL(gemm_nn_had_kernel, dim3((unsigned)g.nunits_pad), dim3(TPB2), lds, h->stream, g);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

@@ -802,6 +802,12 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
             def get_jk_e1(self, *args, **kwargs):
                 return parent._e1_refuse_omega()
             get_j_e1 = get_k_e1 = get_jk_e1
+
+            def get_k_nuc_grad(self, *args, **kwargs):
+                return parent._kg_refuse_omega('get_k_nuc_grad')
+
+            def get_jk_nuc_grad(self, *args, **kwargs):
+                return parent._kg_refuse_omega('get_jk_nuc_grad')
         omega_ = omega
 
         @contextlib.contextmanager
