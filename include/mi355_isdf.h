@@ -392,11 +392,22 @@ int isdf_coulomb_W(isdf_handle h, const double* d_theta, int P, int64_t ldt,
  *                            (1/G inside; honours omega / cutoff / Wigner-Seitz state and the option "coul_sphere")
  *   isdf_spectral_supported: *ok = 1 when isdf_spectral_rows covers this mesh (2-3-5 smooth, (y, z) plane fits LDS)
  *   isdf_spectral_rows:      d_out (nrows, ldx; ldx even, >= 2 npts; padding zeroed) from nrows real rows (ld == G): forward
- *                            plane pass + forward x pass of the own FFT, then the gather; batch rows per pass */
+ *                            plane pass + forward x pass of the own FFT, then the gather; batch rows per pass
+ *   isdf_spectral_rows_lines: the same d_out, bit for bit, with the x pass over the x-lines the points touch only, packing as it
+ *                            goes.  With i = (kx n1 + ky)(n2/2+1) + kz the x-line of i is i mod n1 (n2/2+1):  d_lines = the
+ *                            distinct lines of d_idx ascending, padded with -1 to nlines_pad (a multiple of 16), nlines of them
+ *                            real; d_slot, d_slot_scale (nlines_pad / tile, n0, tile) = the position j in d_idx of the point kx of
+ *                            the tile's line m, or -1, and d_scale[j] (0 where there is no point); tile = what
+ *                            isdf_spectral_lines_tile returns for the mesh (16 up to n0 = 128).  The points of d_idx must be
+ *                            distinct.  A list that covers 90 % of the lines or more takes isdf_spectral_rows. */
 int isdf_coulG_half(isdf_handle h, const int32_t mesh[3], const double a[9], double* d_out);
 int isdf_spectral_supported(isdf_handle h, const int32_t mesh[3], int batch, int* ok);
 int isdf_spectral_rows(isdf_handle h, const double* d_in, int nrows, int64_t ld, const int32_t mesh[3], const int32_t* d_idx,
                        const double* d_scale, int npts, int batch, double* d_out, int64_t ldx);
+int isdf_spectral_rows_lines(isdf_handle h, const double* d_in, int nrows, int64_t ld, const int32_t mesh[3], const int32_t* d_idx,
+                             const double* d_scale, int npts, const int32_t* d_lines, int nlines, int nlines_pad, int tile,
+                             const int32_t* d_slot, const double* d_slot_scale, int batch, double* d_out, int64_t ldx);
+int isdf_spectral_lines_tile(isdf_handle h, const int32_t mesh[3], int* tile);
 /* S4 alone: d_out rows = ifft(coulG * fft(d_in rows)).real (no weight), rows of length G contiguous
  * (ld == ldo == G); in place allowed.  Used by the grid-sharded multi-GPU path, where the rows are
  * assembled by an all-to-all before and scattered by another one after this call. */

@@ -469,13 +469,32 @@ class HipBackend:
         self.handle.call('isdf_coulG_half', _np_ptr(mesh), _np_ptr(a), self._p(out))
         return self.to_host(out).reshape(int(mesh[0]), int(mesh[1]), int(mesh[2]) // 2 + 1)
 
-    def spectral_rows(self, rows, mesh, idx, scale, out, batch=512):
-        """out (n, ldx) <- scale_j (Re, Im) fft(rows)[idx_j] packed as consecutive pairs; rows (n, G) contiguous, idx int32."""
+    def spectral_lines_tile(self, mesh):
+        """The x tile of isdf_spectral_rows_lines on this mesh: the width its slot tables are laid out in."""
+        tile = ctypes.c_int(0)
+        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+        self.handle.call('isdf_spectral_lines_tile', _np_ptr(mesh), ctypes.byref(tile))
+        return int(tile.value)
+
+    def spectral_rows(self, rows, mesh, idx, scale, out, batch=512, lines=None, slot=None, slot_scale=None, nlines=0):
+        """out (n, ldx) <- scale_j (Re, Im) fft(rows)[idx_j] packed as consecutive pairs; rows (n, G) contiguous, idx int32.
+        lines, slot, slot_scale, nlines: the line plan of idx and scale (fit_route.spectral_line_plan, on the device) - the same
+        out, bit for bit, from the x-lines the points touch only (isdf_spectral_rows_lines)."""
         self._stream()
         mesh = np.ascontiguousarray(mesh, dtype=np.int32)
         assert rows.is_contiguous() and out.stride(1) == 1 and idx.dtype == torch.int32 and out.stride(0) % 2 == 0
-        self.handle.call('isdf_spectral_rows', self._p(rows), rows.shape[0], rows.stride(0), _np_ptr(mesh), self._p(idx),
-                         self._p(scale), int(idx.numel()), int(batch), self._p(out), out.stride(0))
+        if lines is None:
+            self.handle.call('isdf_spectral_rows', self._p(rows), rows.shape[0], rows.stride(0), _np_ptr(mesh), self._p(idx),
+                             self._p(scale), int(idx.numel()), int(batch), self._p(out), out.stride(0))
+            return
+        assert lines.dtype == torch.int32 and slot.dtype == torch.int32 and slot_scale.dtype == torch.float64
+        assert lines.is_contiguous() and slot.is_contiguous() and slot_scale.is_contiguous() and slot.dim() == 3
+        tile = slot.shape[2]
+        assert lines.numel() % 16 == 0 and 0 < nlines <= lines.numel() and slot_scale.shape == slot.shape
+        assert tuple(slot.shape) == (lines.numel() // tile, int(mesh[0]), tile)
+        self.handle.call('isdf_spectral_rows_lines', self._p(rows), rows.shape[0], rows.stride(0), _np_ptr(mesh), self._p(idx),
+                         self._p(scale), int(idx.numel()), self._p(lines), int(nlines), int(lines.numel()), int(tile), self._p(slot),
+                         self._p(slot_scale), int(batch), self._p(out), out.stride(0))
 
     def symmetrize_upper(self, W):
         self._stream()

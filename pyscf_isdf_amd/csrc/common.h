@@ -93,6 +93,10 @@ bool conv_rows_q_own_supported(isdf_handle h, const int32_t mesh[3], int nb);
 bool spectral_rows_own_supported(isdf_handle h, const int32_t mesh[3], int nb);
 int spectral_rows_own(isdf_handle h, const double* d_in, int nb, const int32_t mesh[3], const int32_t* d_idx, const double* d_scale,
                       int npts, double* d_out, int64_t ldx, HIP_vector_type<double, 2u>* zbuf);
+int spectral_lines_tile(const int32_t mesh[3]);
+int spectral_rows_lines_own(isdf_handle h, const double* d_in, int nb, const int32_t mesh[3], int npts, const int32_t* d_lines,
+                            int nlines_pad, const int32_t* d_slot, const double* d_slot_scale, double* d_out, int64_t ldx,
+                            HIP_vector_type<double, 2u>* zbuf);
 int conv_rows_q_own(isdf_handle h, const double* d_in, double* d_re, double* d_im, int nb, const int32_t mesh[3], const double* tab,
                     double2* zhalf, double2* zfull);
 int conv_rows_own(isdf_handle h, const double* d_in, double* d_out, int nb, const int32_t mesh[3], const double* cg,
@@ -161,9 +165,10 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
 //   left:  X (m x n, row-major) <- op(L)^-1 X      right: X (n x m, row-major) <- X op(L)^-1      op = L | L^T (trans)
 int trsm_lower_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
 int trsm_lower_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
-// every diagonal block of a block-diagonal lower factor in one launch: X[blk_b, :] <- D_b^-1 X[blk_b, :] (blk_off on the host)
+// every diagonal block of a block-diagonal lower factor in one launch: X[blk_b, :] <- D_b^-1 X[blk_b, :] (blk_off on the host);
+// own_columns: block b solves its own columns [off_b, off_b + nb_b) only (isdf_block_invert: the others are zero and stay so)
 int block_forward_solve(isdf_handle h, const double* D, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
-                        int64_t ldx, int64_t n);
+                        int64_t ldx, int64_t n, bool own_columns = false);
 // X[blk_b, :] <- Dinv_b X[blk_b, :] with explicit block inverses (lower triangular), MFMA kernel of trsm.hip
 int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
                         int64_t ldx, int64_t n, bool square_input = false);

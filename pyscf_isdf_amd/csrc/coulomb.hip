@@ -419,3 +419,41 @@ extern "C" int isdf_spectral_rows(isdf_handle h, const double* d_in, int nrows, 
   }
   return ISDF_OK;
 }
+
+extern "C" int isdf_spectral_lines_tile(isdf_handle h, const int32_t mesh[3], int* tile) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, mesh && tile && mesh[0] > 0);
+  *tile = spectral_lines_tile(mesh);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_spectral_rows_lines(isdf_handle h, const double* d_in, int nrows, int64_t ld, const int32_t mesh[3],
+                                        const int32_t* d_idx, const double* d_scale, int npts, const int32_t* d_lines, int nlines,
+                                        int nlines_pad, int tile, const int32_t* d_slot, const double* d_slot_scale, int batch,
+                                        double* d_out, int64_t ldx) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, mesh && d_lines && d_slot && d_slot_scale && nlines > 0 && nlines <= nlines_pad && nlines_pad % 16 == 0);
+  ARG_CHECK(h, mesh[0] > 0 && tile == spectral_lines_tile(mesh));       // the slot tables are laid out in tiles of this width
+  const int64_t total = (int64_t)mesh[1] * (mesh[2] / 2 + 1);
+  ARG_CHECK(h, nlines <= total);
+  // a list that touches (nearly) every line: the listed pass would move what the plain one moves, through a gather
+  if ((int64_t)nlines * 10 >= total * 9) return isdf_spectral_rows(h, d_in, nrows, ld, mesh, d_idx, d_scale, npts, batch, d_out, ldx);
+  ARG_CHECK(h, d_in && d_out && d_idx && d_scale && nrows >= 0 && batch > 0 && npts > 0);
+  const int64_t G = (int64_t)mesh[0] * mesh[1] * mesh[2];
+  const int64_t gc = (int64_t)mesh[0] * total;
+  ARG_CHECK(h, ld == G && npts <= gc);
+  if (nrows == 0) return ISDF_OK;
+  if (batch > nrows) batch = nrows;
+  if (!spectral_rows_own_supported(h, mesh, batch))
+    return isdf_fail(h, ISDF_ERR_ARG, "isdf_spectral_rows_lines: mesh %d x %d x %d is not covered by the plane FFT", mesh[0], mesh[1],
+                     mesh[2]);
+  double2* Z = (double2*)isdf_ws(h, "coul_Z", sizeof(double2) * (size_t)batch * gc);
+  if (!Z) return ISDF_ERR_HIP;
+  for (int r = 0; r < nrows; r += batch) {
+    const int nb = std::min(batch, nrows - r);
+    int rc = spectral_rows_lines_own(h, d_in + (int64_t)r * ld, nb, mesh, npts, d_lines, nlines_pad, d_slot, d_slot_scale,
+                                     d_out + (int64_t)r * ldx, ldx, Z);
+    if (rc) return rc;
+  }
+  return ISDF_OK;
+}

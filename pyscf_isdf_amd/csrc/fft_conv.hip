@@ -630,6 +630,57 @@ __global__ __launch_bounds__(TPB) void strided_fft_fast_kernel(double2* __restri
   }
 }
 
+// The forward x pass of the packed spectra over a LIST of x-lines, packing as it goes (spectral_rows_lines_own): tile t of a
+// row takes the lines lines[ZCT t ... ZCT t + ZCT - 1] (ascending, -1 = no line: the padding of the last tile) into the layout
+// x[e * ZCT + m] of the kernel above and runs the same fft_fast<-1, ZCT>: a line's butterflies depend neither on its slot m nor
+// on its neighbours, so every value is bit for bit the one strided_fft_fast_kernel<0, ZCT> leaves there.  TPB is a multiple of
+// ZCT: a thread keeps one slot m, one line.  Nothing goes back to the lines: slot[t][e][m] (the tile's own layout, so the loads
+// coalesce; -1 = not a packed point) names the packed position j of the point e of line m, slot_scale[t][e][m] its scale, and
+// the scaled value goes from LDS straight to out[row][j] (spectral_pack_kernel's arithmetic); tile 0 writes the zero padding
+// [npts, ldx2) of its row.  The slots are fetched before the transform, the scales after it (133 VGPRs otherwise: 3 waves).
+template <int ZCT>
+__global__ __launch_bounds__(TPB) void strided_fft_lines_kernel(const double2* __restrict__ data, int64_t os, int64_t es, Axis ax,
+                                                                int ntile, const int32_t* __restrict__ lines,
+                                                                const int32_t* __restrict__ slot,
+                                                                const double* __restrict__ slot_scale, int npts,
+                                                                double2* __restrict__ out, int64_t ldx2) {
+  static_assert(TPB % ZCT == 0, "one slot per thread");
+  constexpr int KS = 2048 / TPB;
+  extern __shared__ double2 lds[];
+  const int n = ax.n;
+  double2* x = lds;
+  double2* tw = lds + n * ZCT;
+  for (int k = threadIdx.x; k < n; k += TPB) tw[k] = ax.tw[k];
+  const int64_t outer = blockIdx.x / ntile;
+  const int t = blockIdx.x % ntile;
+  const int l = lines[t * ZCT + (threadIdx.x & (ZCT - 1))];
+  const double2* base = data + outer * os + l;
+  if (l >= 0)
+    for (int c = threadIdx.x; c < n * ZCT; c += TPB) x[c] = base[(int64_t)(c / ZCT) * es];
+  const int64_t tile0 = (int64_t)t * n * ZCT;
+  int js[KS];
+#pragma unroll
+  for (int k = 0; k < KS; ++k) {
+    const int c = threadIdx.x + k * TPB;
+    js[k] = (c < n * ZCT) ? slot[tile0 + c] : -1;
+  }
+  __syncthreads();
+  fft_fast<-1, ZCT>(x, ax, ZCT, tw);
+  double2* o = out + outer * ldx2;
+  double sc[KS];
+#pragma unroll
+  for (int k = 0; k < KS; ++k) sc[k] = (js[k] >= 0) ? slot_scale[tile0 + threadIdx.x + k * TPB] : 0.0;
+#pragma unroll
+  for (int k = 0; k < KS; ++k)
+    if (js[k] >= 0) {
+      const double2 v = x[threadIdx.x + k * TPB];
+      const double s = sc[k];
+      o[js[k]] = make_double2(v.x * s, v.y * s);
+    }
+  if (t == 0)
+    for (int64_t j = npts + threadIdx.x; j < ldx2; j += TPB) o[j] = make_double2(0.0, 0.0);
+}
+
 // ---- PLANE path: z and y transforms of one (y, z) plane fused in LDS: three passes instead of five ---------------------------
 // A workgroup of 1024 threads owns the plane of one (row, x): n1 real lines of n2 points = 115 KB at 120^3, the half-complex plane
 // n1 x (n2/2+1) = 117 KB - the whole of it stays in LDS between the z and the y transform, so the pair
@@ -1321,6 +1372,37 @@ int spectral_rows_own(isdf_handle h, const double* d_in, int nb, const int32_t m
   const int64_t ldx2 = ldx / 2;
   spectral_pack_kernel<<<dim3((unsigned)cdiv(ldx2, 256), (unsigned)nb), dim3(256), 0, h->stream>>>(zbuf, gc, d_idx, d_scale, npts,
                                                                                                   (double2*)d_out, ldx2);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+// spectral_rows_own with the x pass over the listed x-lines only, packing as it goes (strided_fft_lines_kernel): the lines are
+// read once and nothing but X is written.  d_lines = the distinct x-lines idx % (n1 n2h) of the packed points in ascending
+// order, padded with -1 to nlines_pad (a multiple of 16: every x tile divides it); d_slot, d_slot_scale (nlines_pad / tile, n0,
+// tile): the packed position of the point (line, kx) or -1, and its scale; tile = spectral_lines_tile(mesh).  Bit for bit
+// spectral_rows_own's X.
+int spectral_lines_tile(const int32_t mesh[3]) { return fast_lines(mesh[0]); }
+
+int spectral_rows_lines_own(isdf_handle h, const double* d_in, int nb, const int32_t mesh[3], int npts, const int32_t* d_lines,
+                            int nlines_pad, const int32_t* d_slot, const double* d_slot_scale, double* d_out, int64_t ldx,
+                            double2* zbuf) {
+  const int n0 = mesh[0], n1 = mesh[1], n2 = mesh[2], n2h = n2 / 2 + 1;
+  Axis ax[3];
+  if (int rc = make_axes(h, mesh, ax, "spectral_rows_lines_own")) return rc;
+  const int64_t gc = (int64_t)n0 * n1 * n2h;
+  const PlaneGeo geo = plane_geometry(n1, n2, false);
+  const int FX = fast_lines(n0);
+  ARG_CHECK(h, geo.bytes && FX >= 1 && (int64_t)nb * n0 < 2147483647LL && nb <= 65535 && (ldx & 1) == 0 && ldx >= 2 * (int64_t)npts);
+  ARG_CHECK(h, d_lines && d_slot && d_slot_scale && nlines_pad >= 16 && nlines_pad % 16 == 0 &&
+                   (int64_t)nb * (nlines_pad / FX) < 2147483647LL);
+  ProfScope ps(h, "spectral_rows_own[byte]", (8.0 * (double)n0 * n1 * n2 + 8.0 * (double)ldx) * nb, 2);
+  if (int rc = launch_plane_fwd(h, d_in, zbuf, ax, geo, (int)((int64_t)nb * n0), PIPE_ANY)) return rc;
+  const int nt = nlines_pad / FX;
+  with_lines(FX, [&](auto z) {
+    strided_fft_lines_kernel<decltype(z)::value><<<dim3((unsigned)((int64_t)nb * nt)), dim3(TPB), sizeof(double2) * ((size_t)n0 * FX + n0),
+                                                   h->stream>>>(zbuf, gc, (int64_t)n1 * n2h, ax[0], nt, d_lines, d_slot, d_slot_scale,
+                                                                npts, (double2*)d_out, ldx / 2);
+  });
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

@@ -427,23 +427,23 @@ extern "C" int isdf_block_solve(isdf_handle h, const double* d_D, int P, int nbl
 }
 
 namespace {
-__global__ void block_identity_kernel(double* __restrict__ E, int P, const int32_t* __restrict__ blk_of_row) {
-  // E (P x P) <- 0 with ones on the diagonal (the right-hand side whose block solves are the block inverses)
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < (int64_t)P * P) E[i] = (i / P == i % P) ? 1.0 : 0.0;
-  (void)blk_of_row;
+__global__ void block_identity_kernel(double* __restrict__ E, int P, int n) {
+  // ones on the first n diagonal entries of E (P x P, zeroed before): the right-hand side whose block solves are the inverses
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) E[(int64_t)i * P + i] = 1.0;
 }
 }  // namespace
 
 extern "C" int isdf_block_invert(isdf_handle h, const double* d_D, int P, int nblk, const int32_t* blk_off, double* d_Dinv) {
   // Dinv <- blockdiag(D_b^-1): forward solves of the block factors against the identity.  Entries above the diagonal and
-  // outside the blocks are exact zeros (forward substitution of a unit vector never touches the rows above it).
+  // outside the blocks are exact zeros (forward substitution of a unit vector never touches the rows above it), so only the
+  // columns of a block's own diagonal block are solved; the rest is the memset's +0.0.
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_D && d_Dinv && blk_off && P > 0 && nblk > 0 && blk_off[0] == 0 && blk_off[nblk] <= P);
-  hipLaunchKernelGGL(block_identity_kernel, dim3((unsigned)cdiv((int64_t)P * P, 256)), dim3(256), 0, h->stream, d_Dinv, P,
-                     (const int32_t*)nullptr);
+  HIP_TRY(h, hipMemsetAsync(d_Dinv, 0, sizeof(double) * (size_t)P * (size_t)P, h->stream));
+  hipLaunchKernelGGL(block_identity_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, h->stream, d_Dinv, P, P);
   KERNEL_CHECK(h);
-  return block_forward_solve(h, d_D, P, nblk, blk_off, d_Dinv, P, P);
+  return block_forward_solve(h, d_D, P, nblk, blk_off, d_Dinv, P, P, true);
 }
 
 extern "C" int isdf_block_apply(isdf_handle h, const double* d_Dinv, int64_t ldd, int nblk, const int32_t* blk_off,

@@ -81,12 +81,13 @@ __global__ void transpose_kernel(const double* __restrict__ src, int64_t lds, in
 // HBM traffic = one read and one write of X (rocBLAS dtrsm block by block moves the same data at about 1 TB/s).
 __global__ __launch_bounds__(256) void block_forward_kernel(const double* __restrict__ D, int64_t ldd,
                                                             const int32_t* __restrict__ blk_off,
-                                                            double* __restrict__ X, int64_t ldx, int64_t n) {
+                                                            double* __restrict__ X, int64_t ldx, int64_t n, int own_columns) {
   const int b = blockIdx.y;
   const int off = blk_off[b], m = blk_off[b + 1] - off;
   if (m <= 0) return;
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= n) return;
+  // own_columns: the column window [off, off + m) of this block (a lane's column does not depend on the others)
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x + (own_columns ? off : 0);
+  if (c >= (own_columns ? min(n, (int64_t)off + m) : n)) return;
   const double* Db = D + (int64_t)off * ldd + off;
   double* Xb = X + (int64_t)off * ldx + c;
   const int nsub = (m + 63) >> 6;
@@ -401,17 +402,22 @@ int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk
 }
 
 int block_forward_solve(isdf_handle h, const double* D, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
-                        int64_t ldx, int64_t n) {
+                        int64_t ldx, int64_t n, bool own_columns) {
   ARG_CHECK(h, D && X && blk_off_host && nblk > 0 && n > 0 && nblk <= 65535);
   int32_t* d_off = (int32_t*)isdf_ws(h, "trsm_blk_off", sizeof(int32_t) * (size_t)(nblk + 1));
   if (!d_off) return ISDF_ERR_HIP;
   HIP_TRY(h, hipMemcpyAsync(d_off, blk_off_host, sizeof(int32_t) * (size_t)(nblk + 1), hipMemcpyHostToDevice, h->stream));
   double rows2 = 0.0;
-  for (int b = 0; b < nblk; ++b) rows2 += (double)(blk_off_host[b + 1] - blk_off_host[b]) * (blk_off_host[b + 1] - blk_off_host[b]);
-  ProfScope ps(h, "block_forward_kernel[byte]", 16.0 * (double)blk_off_host[nblk] * (double)n);
-  (void)rows2;
-  hipLaunchKernelGGL(block_forward_kernel, dim3((unsigned)cdiv(n, 256), (unsigned)nblk), dim3(256), 0, h->stream, D, ldd, d_off,
-                     X, ldx, n);
+  int64_t widest = 0;
+  for (int b = 0; b < nblk; ++b) {
+    rows2 += (double)(blk_off_host[b + 1] - blk_off_host[b]) * (blk_off_host[b + 1] - blk_off_host[b]);
+    widest = std::max<int64_t>(widest, blk_off_host[b + 1] - blk_off_host[b]);
+  }
+  if (own_columns && widest <= 0) return ISDF_OK;
+  const int64_t ncol = own_columns ? widest : n;         // columns a block walks
+  ProfScope ps(h, "block_forward_kernel[byte]", 16.0 * (own_columns ? rows2 : (double)blk_off_host[nblk] * (double)n));
+  hipLaunchKernelGGL(block_forward_kernel, dim3((unsigned)cdiv(ncol, 256), (unsigned)nblk), dim3(256), 0, h->stream, D, ldd, d_off,
+                     X, ldx, n, own_columns ? 1 : 0);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

@@ -3,6 +3,30 @@ probe-density check that guards the block-Jacobi route.  Mixed into ``isdf.ISDF`
 import numpy as np
 
 
+def spectral_line_plan(idx, scale, mesh, tile):
+    """The x-lines a list of half-spectrum points touches (isdf_spectral_rows_lines).  With i = (kx n1 + ky) n2h + kz the x-line
+    of i is i mod (n1 n2h) and kx = i div (n1 n2h).  Returns (lines, slot, slot_scale, nlines): the distinct lines ascending,
+    padded with -1 to a multiple of 16 (the widest x tile; the narrower ones divide it); slot (len(lines) / tile, n0, tile) int32
+    = the position j in idx of the point kx of line m of a tile, or -1 (the layout the x pass holds a tile in); slot_scale, of
+    the same shape = scale[j], 0 where there is no point; the number of real lines.  tile: backend.spectral_lines_tile(mesh).
+    None when idx names a point twice (a slot holds one j)."""
+    idx = np.asarray(idx, dtype=np.int64)
+    n0, n1, n2 = (int(x) for x in mesh)
+    per = n1 * (n2 // 2 + 1)
+    line, kx = idx % per, idx // per
+    real = np.unique(line)
+    lines = np.full(-(-len(real) // 16) * 16, -1, dtype=np.int32)
+    lines[:len(real)] = real
+    slot = np.full((len(lines), n0), -1, dtype=np.int32)
+    where = np.searchsorted(real, line)
+    slot[where, kx] = np.arange(len(idx), dtype=np.int32)
+    if np.count_nonzero(slot >= 0) != len(idx):
+        return None
+    slot = np.ascontiguousarray(slot.reshape(-1, tile, n0).transpose(0, 2, 1))
+    slot_scale = np.where(slot >= 0, np.asarray(scale, dtype=np.float64)[np.maximum(slot, 0)], 0.0)
+    return lines, slot, slot_scale, len(real)
+
+
 class FitRouteMixin:
     # ---- S3c helpers (block-Jacobi route) ---------------------------------------------------------------
     def _bj_prepare(self, ao, nh, d_ip, ip_off, aoP, scratch=None):
@@ -209,7 +233,7 @@ class FitRouteMixin:
         # (one plan per kernel state of the backend: the table comes down to the host and the point list goes up again)
         epoch = getattr(be, 'kernel_epoch', None)
         ckey = (tuple(int(x) for x in mesh), epoch, str(getattr(self, 'w_sphere', 'auto')), float(getattr(self, 'w_sphere_tol', 0.0)),
-                int(self.fft_batch or 512), int(getattr(self, 'w_sort_bins', 0) or 0))
+                int(self.fft_batch or 512), int(getattr(self, 'w_sort_bins', 0) or 0), bool(getattr(self, 'w_spectral_lines', True)))
         cached = getattr(self, '_spectral_plan_cache', None)
         if epoch is not None and cached is not None and cached[0] == ckey:
             return cached[1]
@@ -243,7 +267,20 @@ class FitRouteMixin:
         scale = np.sqrt(mult.ravel()[idx] * w * cg.ravel()[idx])
         npts = len(idx)
         ldx = -(-2 * npts // 128) * 128
-        return dict(idx=be.to_device(idx), scale=be.to_device(scale), npts=npts, ldx=ldx, fraction=2.0 * npts / G)
+        # (the line plan goes up with the list: like it, it depends on the mesh, the cell and the kernel table only)
+        return dict(idx=be.to_device(idx), scale=be.to_device(scale), npts=npts, ldx=ldx, fraction=2.0 * npts / G,
+                    lines_kw=self._spectral_lines_kw(idx, scale, mesh))
+
+    def _spectral_lines_kw(self, idx, scale, mesh):
+        """The line plan of a point list (spectral_line_plan) on the device, as the keywords of be.spectral_rows; {} (every line,
+        then the gather) when the backend has no isdf_spectral_rows_lines, w_spectral_lines is off or idx names a point twice."""
+        be = self.backend
+        if not hasattr(be, 'spectral_lines_tile') or not getattr(self, 'w_spectral_lines', True):
+            return {}
+        lp = spectral_line_plan(idx, scale, mesh, be.spectral_lines_tile(mesh))
+        if lp is None:
+            return {}
+        return dict(lines=be.to_device(lp[0]), slot=be.to_device(lp[1]), slot_scale=be.to_device(lp[2]), nlines=lp[3])
 
     def _spectral_point_set(self, mesh, box, share):
         """The packed points of a spectral W build, without any kernel scale (shared by the Gamma-point plan above and the k-point
@@ -319,7 +356,7 @@ class FitRouteMixin:
         scale = np.sqrt(mult.ravel()[idx] * w * cg.ravel()[idx])
         ldx = -(-2 * len(idx) // 128) * 128
         X = be.empty((ntest, ldx))
-        be.spectral_rows(t, mesh, be.to_device(idx), be.to_device(scale), X, batch=ntest)
+        be.spectral_rows(t, mesh, be.to_device(idx), be.to_device(scale), X, batch=ntest, **self._spectral_lines_kw(idx, scale, mesh))
         x = be.to_host(X)[:, :2 * len(idx)]
         e = x[:, 0::2] ** 2 + x[:, 1::2] ** 2
         outside = ~keep.ravel()[idx]
@@ -374,7 +411,7 @@ class FitRouteMixin:
             rows = scratch[:take]
             if probe is not None:
                 be.rows_combine(probe[0][:, g0:g0 + take], rows, probe[1], accumulate=g0 > 0)
-            be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[g0:g0 + take], batch=take)
+            be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[g0:g0 + take], batch=take, **plan['lines_kw'])
             if fill > take:
                 scratch[:fill - take].copy_(scratch[take:fill].clone() if fill - take > take else scratch[take:fill])
             g0 += take
@@ -432,7 +469,7 @@ class FitRouteMixin:
                 rows = scratch[:end - app]
                 if probe is not None:
                     be.rows_combine(probe[0][:, app:end], rows, probe[1], accumulate=app > 0)
-                be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[app:end], batch=min(nbat, end - app))
+                be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[app:end], batch=min(nbat, end - app), **plan['lines_kw'])
                 tail = prod - end
                 if tail > 0:
                     src = scratch[end - app:prod - app]

@@ -68,6 +68,8 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                                           # sphere <= w_sphere_tol, measured once per mesh), the classic build otherwise
         self.w_sphere_tol = 1e-11
         self.w_sort_bins = 256            # packed points sorted into this many shells of |G|^2, outermost first (0: as they lie in the half spectrum)
+        self.w_spectral_lines = True      # the x pass of the packed spectra walks the x-lines the points touch only and packs as it goes
+                                          # (fit_route.spectral_line_plan); False: every line, then the gather - the same X, bit for bit
         self.w_spectral_check_tol = 5e-9  # the spectral form is kept only when the route's probe mismatch stays below this (the classic form
                                           # is held to bj_check_tol): its rounding, amplified like the classic form's, shows up there first
         self.w_spectral_max_c = 18        # the spectral form carries a few times the classic product's rounding (both operands come out of a

@@ -502,7 +502,7 @@ class KPointMixin:
                 on_nyq |= (i == n // 2)
         d_idx = be.to_device(idx)
         X = self._buffer('kspecX', (P, ldx))
-        be.spectral_rows(Y, mesh, d_idx, be.to_device(np.ones(npts)), X, batch=nbat)
+        be.spectral_rows(Y, mesh, d_idx, be.to_device(np.ones(npts)), X, batch=nbat, **self._spectral_lines_kw(idx, np.ones(npts), mesh))
         self.w_spectral_fraction = 2.0 * npts / G
         return dict(X=X, idx=d_idx, npts=npts, ldx=ldx, pair_exact=not on_nyq.any(), strip=nbat,
                     s=self._buffer('kspec_s', (ldx,)), a=self._buffer('kspec_a', (ldx,)))

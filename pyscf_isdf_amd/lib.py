@@ -91,6 +91,9 @@ SIGNATURES = {
     'isdf_coulG_half': (c_int, [c_vp, c_vp, c_vp, c_vp]),
     'isdf_spectral_supported': (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(c_int)]),
     'isdf_spectral_rows': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_i64]),
+    'isdf_spectral_rows_lines': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp,
+                                         c_int, c_vp, c_i64]),
+    'isdf_spectral_lines_tile': (c_int, [c_vp, c_vp, c_vp]),
     'isdf_coulomb_rows_q': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     'isdf_nyquist_spectra': (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_vp]),
     'isdf_zhadamard_planes': (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_i64]),

@@ -472,7 +472,7 @@ class ShardedMixin:
             for (s0, s1), piece in zip(slices, recv):
                 rows_full[:, s0:s1] = piece
             if mine:
-                be.spectral_rows(rows_full, mesh, plan['idx'], plan['scale'], Xb[:mine], batch=mine)
+                be.spectral_rows(rows_full, mesh, plan['idx'], plan['scale'], Xb[:mine], batch=mine, **plan['lines_kw'])
             got = views(recvX, lambda q: nrow[q], lambda q: kw)
             comm.all_to_all(got, [Xb[:mine, k0:k1].contiguous() for k0, k1 in ks])
             for q in range(R):
