@@ -1,6 +1,14 @@
 """The fit routes of the ISDF build: block-Jacobi helpers (S3c), route selection, and the
 probe-density check that guards the block-Jacobi route.  Mixed into ``isdf.ISDF``; host orchestration only."""
+import warnings
 import numpy as np
+
+# what follows a failed probe check, per kind of fit state (the end of the warning)
+_PROBE_FAILED = {
+    'blockjacobi': '; rebuilding W with the Cholesky route',
+    'blockjacobi-spectral': ' in the spectral build; rebuilding W the classic way',
+    'blockjacobi-paneled': ' in a paneled build, where the Cholesky route is not available: rebuilding with pairs of clusters '
+                           'merged into one preconditioner block'}
 
 
 def spectral_line_plan(idx, scale, mesh, tile):
@@ -64,25 +72,29 @@ class FitRouteMixin:
             self._Dinv, self._Dinv_key = Dinv, key
         return self._Dinv
 
-    def _bj_rows(self, aoP, nh, ao, ng, Dblk, ip_off, out):
-        """out (P, ng) <- Y' = D^-1 (aoP ao)^2 on ng grid columns."""
+    def _bj_rows(self, aoP, ao, ng, Dblk, ip_off, out, nh=0, r0=0, r1=None):
+        """out (r1 - r0, ng) <- rows r0:r1 (on block boundaries; default: all of them) of Y' = D^-1 (pair rows) on ng grid columns:
+        the pair rows of those points, forward solves with their own diagonal blocks only.  nh: the k-point stack."""
         be = self.backend
         Dinv = self._block_inverse(Dblk, ip_off)
-        if getattr(self, '_psi', None) is not None and not nh:
-            be.pair_prod_rows(aoP, self._psiP, ao, self._psi, ng, out)      # (AO x occupied) pair space
-            if Dinv is not None:
-                be.block_apply(Dinv, ip_off, out)
-            else:
-                be.block_solve(Dblk, ip_off, 0, 0, out)
-            return
-        if Dinv is not None and not nh:
-            be.pair_rows_block_apply(aoP, ao, ng, Dinv, ip_off, out)        # the square rides the block apply's staging
-            return
-        be.pair_gram_rows(aoP, ao, ng, out, nh)
+        ip_off = np.asarray(ip_off)
+        r1 = int(ip_off[-1]) if r1 is None else r1
+        i0, i1 = int(np.searchsorted(ip_off, r0)), int(np.searchsorted(ip_off, r1))
+        assert ip_off[i0] == r0 and ip_off[i1] == r1
+        sub = (ip_off[i0:i1 + 1] - r0).astype(np.int32)
+        aoP, Dblk = aoP[r0:r1], Dblk[r0:r1, r0:r1]
         if Dinv is not None:
-            be.block_apply(Dinv, ip_off, out)
+            Dinv = Dinv[r0:r1, r0:r1]
+        if getattr(self, '_psi', None) is not None and not nh:
+            be.pair_prod_rows(aoP, self._psiP[r0:r1], ao, self._psi, ng, out)   # (AO x occupied) pair space
+        elif Dinv is not None and not nh:
+            return be.pair_rows_block_apply(aoP, ao, ng, Dinv, sub, out)        # the square rides the block apply's staging
         else:
-            be.block_solve(Dblk, ip_off, 0, 0, out)
+            be.pair_gram_rows(aoP, ao, ng, out, nh)
+        if Dinv is not None:
+            be.block_apply(Dinv, sub, out)
+        else:
+            be.block_solve(Dblk, sub, 0, 0, out)
 
     # ---- paneled S3c/S4/S5: more fit rows than HBM holds at once -------------------------------------------------
     def _resident_rows(self, G, P):
@@ -140,27 +152,30 @@ class FitRouteMixin:
                 return panels
             npan += 1
 
-    def _bj_rows_range(self, r0, r1, out):
-        """out (r1 - r0, G) <- rows r0:r1 of Y' = D^-1 (aoP ao)^2 (r0, r1 on block boundaries): pair-gram rows of those
-        points, forward solves with their own diagonal blocks only."""
-        be, st = self.backend, self._fit_state
-        ip_off = np.asarray(st['ip_off'])
-        i0, i1 = int(np.searchsorted(ip_off, r0)), int(np.searchsorted(ip_off, r1))
-        assert ip_off[i0] == r0 and ip_off[i1] == r1
-        G = self.ao.shape[1]
-        Dinv = self._block_inverse(st['Dblk'], ip_off)
-        sub = (ip_off[i0:i1 + 1] - r0).astype(np.int32)
-        if getattr(self, '_psi', None) is not None:
-            be.pair_prod_rows(self.aoP[r0:r1], self._psiP[r0:r1], self.ao, self._psi, G, out)
-            if Dinv is not None:
-                be.block_apply(Dinv[r0:r1, r0:r1], sub, out)
-            else:
-                be.block_solve(st['Dblk'][r0:r1, r0:r1], sub, 0, 0, out)
-        elif Dinv is not None:
-            be.pair_rows_block_apply(self.aoP[r0:r1], self.ao, G, Dinv[r0:r1, r0:r1], sub, out)
-        else:
-            be.pair_gram_rows(self.aoP[r0:r1], self.ao, G, out, 0)
-            be.block_solve(st['Dblk'][r0:r1, r0:r1], sub, 0, 0, out)
+    def _bj_row_batches(self, r0, r1, nbat, scratch):
+        """The fit rows of [r0, r1) (block boundaries), produced in the row scratch (nbat + largest block, G): yields
+        (first_row, rows_view) in batches of exactly nbat rows, the last one ragged.  The rows arrive block by block (a block's
+        solve needs all of its rows) but leave in batches of one size - one FFT plan, full GEMM tiles: the scratch is filled with
+        whole blocks until a batch is in, and what overshoots it moves to the front when the consumer comes back for more."""
+        st = self._fit_state
+        ip_off = np.asarray(st['ip_off'], dtype=np.int64)
+        cap, G = scratch.shape
+        nxt, fill, g0 = r0, 0, r0                      # next row to produce, rows waiting in the scratch, their first index
+        while nxt < r1 or fill > 0:
+            while fill < nbat and nxt < r1:
+                j = int(np.searchsorted(ip_off, nxt)) + 1
+                while j + 1 < len(ip_off) and ip_off[j + 1] <= r1 and fill + (ip_off[j + 1] - nxt) <= cap:
+                    j += 1
+                b1 = int(ip_off[j])
+                self._bj_rows(self.aoP, self.ao, G, st['Dblk'], st['ip_off'], scratch[fill:fill + (b1 - nxt)], r0=nxt, r1=b1)
+                fill += b1 - nxt
+                nxt = b1
+            take = min(nbat, fill)
+            yield g0, scratch[:take]
+            if fill > take:
+                scratch[:fill - take].copy_(scratch[take:fill].clone() if fill - take > take else scratch[take:fill])
+            g0 += take
+            fill -= take
 
     def _finish_W_paneled(self, W, probe=None):
         """S3c + S4 + S5 when the P fit rows do not fit into HBM together (c_isdf above ~10 at configs[2] on one GPU).
@@ -184,35 +199,17 @@ class FitRouteMixin:
         nbat = int(self.fft_batch or 512)
         big = int(np.diff(ip_off).max())
         self._last_fft_batch = nbat
-        # recomputed rows arrive block by block (a block's solve needs all of its rows) but leave in batches of exactly nbat
-        # rows - one FFT plan, full GEMM tiles: the scratch holds a batch plus the block that overshoots it
-        scratch = self._buffer('rows_scratch', (nbat + big, G))
+        scratch = self._buffer('rows_scratch', (nbat + big, G))       # for the recomputed rows (_bj_row_batches)
         for q, (q0, q1) in enumerate(panels):
             Yq = buf[:q1 - q0]
-            self._bj_rows_range(q0, q1, Yq)
+            self._bj_rows(self.aoP, self.ao, G, st['Dblk'], st['ip_off'], Yq, r0=q0, r1=q1)
             be.coulomb_W(Yq, mesh, a, 0, q1 - q0, min(nbat, q1 - q0), W[q0:q1, q0:q1], upper_only=True)
             if probe is not None:
                 be.rows_combine(probe[0][:, q0:q1], Yq, probe[1], accumulate=q > 0)
             for p0, p1 in panels[:q]:
-                nxt, fill, g0 = p0, 0, p0              # next row to recompute, rows waiting in the scratch, their first index
-                while nxt < p1 or fill > 0:
-                    while fill < nbat and nxt < p1:
-                        i = int(np.searchsorted(ip_off, nxt))
-                        j = i + 1
-                        while j + 1 < len(ip_off) and ip_off[j + 1] <= p1 and fill + (ip_off[j + 1] - nxt) <= nbat + big:
-                            j += 1
-                        b1 = int(ip_off[j])
-                        self._bj_rows_range(nxt, b1, scratch[fill:fill + (b1 - nxt)])
-                        fill += b1 - nxt
-                        nxt = b1
-                    take = min(nbat, fill)
-                    V = scratch[:take]
-                    be.coulomb_rows(V, mesh, a, take)
-                    be.gemm_nt(V, Yq, W[g0:g0 + take, q0:q1], alpha=w)
-                    if fill > take:
-                        scratch[:fill - take].copy_(scratch[take:fill].clone() if fill - take > take else scratch[take:fill])
-                    g0 += take
-                    fill -= take
+                for g0, V in self._bj_row_batches(p0, p1, nbat, scratch):
+                    be.coulomb_rows(V, mesh, a, V.shape[0])
+                    be.gemm_nt(V, Yq, W[g0:g0 + V.shape[0], q0:q1], alpha=w)
         be.symmetrize_upper(W)
         self._bj_finish(st['Afac'], st['Dblk'], st['ip_off'], W)
 
@@ -396,26 +393,11 @@ class FitRouteMixin:
         if piece:
             self._spectral_rows_two_frontiers(X, scratch, piece, plan, probe)
             return self._spectral_W_finish(X, W, nbat)
-        nxt, fill, g0 = 0, 0, 0
-        while nxt < P or fill > 0:
-            while fill < nbat and nxt < P:
-                i = int(np.searchsorted(ip_off, nxt))
-                j = i + 1
-                while j + 1 < len(ip_off) and fill + (ip_off[j + 1] - nxt) <= nbat + big:
-                    j += 1
-                b1 = int(ip_off[j])
-                self._bj_rows_range(nxt, b1, scratch[fill:fill + (b1 - nxt)])
-                fill += b1 - nxt
-                nxt = b1
-            take = min(nbat, fill)
-            rows = scratch[:take]
+        for g0, rows in self._bj_row_batches(0, P, nbat, scratch):
+            take = rows.shape[0]
             if probe is not None:
                 be.rows_combine(probe[0][:, g0:g0 + take], rows, probe[1], accumulate=g0 > 0)
             be.spectral_rows(rows, mesh, plan['idx'], plan['scale'], X[g0:g0 + take], batch=take, **plan['lines_kw'])
-            if fill > take:
-                scratch[:fill - take].copy_(scratch[take:fill].clone() if fill - take > take else scratch[take:fill])
-            g0 += take
-            fill -= take
         self._spectral_W_finish(X, W, nbat)
 
     def _spectral_W_finish(self, X, W, nbat):
@@ -628,9 +610,51 @@ class FitRouteMixin:
         does not see the cond(A')-amplified rounding of M'; their largest relative difference is returned.
         aoT_P: (nao, P), or a list of such planes whose densities are added (k-points: Re/Im u^k at the points, the
         density sum_k u^k* R u^k with real symmetric R; W = the real plane of W^{q=0})."""
-        be = self.backend
+        F, T0 = self._bj_probe_fitted(aoT_P, Afac, Dblk, ip_off, Yp, ng)[1:]
+        return self._bj_probe_energies(T0, F, self.W if W is None else W, grid_slice)
+
+    def _bj_probe_fitted(self, aoT_P, Afac, Dblk, ip_off, Yp, ng):
+        """(E, F, T0) from resident fit rows Yp: the probes' combination rows, their fitted densities F = E Y' (n, ng) in one pass
+        over Y' (isdf_bj_probe_rows), the probe densities at the points."""
         T = self._bj_probe_densities(aoT_P)
         T0 = T.clone()
-        F = be.empty((T.shape[0], ng))
-        be.bj_probe_rows(T, Afac, Dblk, ip_off, Yp, ng, F)
-        return self._bj_probe_energies(T0, F, self.W if W is None else W, grid_slice)
+        F = self.backend.empty((T.shape[0], ng))
+        self.backend.bj_probe_rows(T, Afac, Dblk, ip_off, Yp, ng, F)
+        return T, F, T0
+
+    def _probe_setup(self, Afac, Dblk, ip_off, width, aoT=None, d_ip=None, rows=None):
+        """The route check, first half.  None unless fit_route == 'auto'; else (E, F, T0): the probes' combination rows (n, P), their
+        fitted densities F = E Y' (n, width) - formed here when the fit rows are resident (rows), else room for what the row pass
+        accumulates (probe[0], probe[1] of _finish_W_paneled / _finish_W_spectral / _finish_W_sharded_spectral) - and the probe
+        densities at the points.  aoT: phi at the points (nao, P) where the sharded build holds it; gathered with d_ip otherwise."""
+        if self.fit_route != 'auto':
+            return None
+        be = self.backend
+        if aoT is None:
+            aoT = be.empty((self.ao.shape[0], len(self.ip)))
+            be.gather_cols(self.ao, d_ip, aoT)
+        if rows is not None:
+            return self._bj_probe_fitted(aoT, Afac, Dblk, ip_off, rows, width)
+        T0, E = self._bj_probe_vectors(aoT, Afac, Dblk, ip_off)
+        return E, be.empty((E.shape[0], width)), T0
+
+    def _probe_verdict(self, probe, t0, warn=True):
+        """The route check, second half, for the W just built from the fit in self._fit_state: bj_check <- the probes' mismatch
+        (one value on all ranks), held to bj_check_tol - the spectral form to w_spectral_check_tol as well.  Returns (passed, t0);
+        a failure warns (the text names what the caller does next) and takes back w_spectral_fraction."""
+        st = self._fit_state
+        sharded = st.get('sharded')
+        check = self._bj_probe_energies(probe[2], probe[1], self.W, self._slice if sharded else None)
+        # (replicated W, all-reduced probe energies; the max over ranks makes the decision identical everywhere)
+        self.bj_check = self.comm.agree_max(check) if sharded else check
+        t0 = self._tick('S5_route_check', t0)
+        spectral = st['kind'] == 'blockjacobi-spectral'
+        tol = min(self.bj_check_tol, self.w_spectral_check_tol) if spectral else self.bj_check_tol
+        if self.bj_check <= tol:
+            return True, t0
+        if warn:
+            warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e)%s'
+                          % (self.bj_check, tol, _PROBE_FAILED[st['kind']]))
+        if spectral:
+            self.w_spectral_fraction = None
+        return False, t0

@@ -17,7 +17,6 @@ the probe check), ``sharded`` (grid-sharded multi-GPU build), ``kpoints`` (k-poi
 import os
 import sys
 import time
-import warnings
 import numpy as np
 import torch
 from . import gto
@@ -85,10 +84,11 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         self.reg_rel = 1e-12             # relative diagonal shift of A_PP in the global fit
         self.reg_used = 0.0
         self.k_ip_factor = None           # k-points: points = c_isdf * nao * k_ip_factor (default min(nk, 2))
-        self.kpt_pair_q = 'auto'          # k-points: True = build one W^q per +-q pair and use W^{-q} = conj(W^q) (half the products);
-                                          # exact on odd meshes only - on an even mesh the Nyquist index has no partner and the
-                                          # wrap-around rule zeroes it for one sign of q (MgO 2x2x2 / 64^3: 7e-6 in K); False =
-                                          # every q from its own kernel table; 'auto' = pair on all-odd meshes only
+        self.kpt_pair_q = 'auto'          # k-points: 'auto' / True = build one W^q per +-q pair and use W^{-q} = conj(W^q) (half the
+                                          # products), adding on an even mesh the Nyquist-plane terms the pairing misses (the Nyquist
+                                          # index has no partner and the wrap-around rule zeroes it for one sign of q: MgO 2x2x2 /
+                                          # 64^3 reads 7e-6 in K without them; kpoints._nyquist_pair_correction); 'uncorrected' = the
+                                          # pairing without those terms; False = every q from its own kernel table
         self.kpt_w_spectral = False       # k-points: True = every M^q from ONE packed half spectrum X of the (real, q-independent) fit rows:
                                           # per q two table-scaled products over X in one pass (isdf_herm_kscale_nt), no FFT; the points
                                           # kept follow w_sphere / w_sphere_tol / w_sort_bins as at the Gamma point (inside the sphere the
@@ -383,14 +383,7 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         cell, be = self.cell, self.backend
         nao, G = self.ao.shape
         a = np.asarray(cell.lattice_vectors(), dtype=float)
-        owner = be.partition_by_atom(self.grids.coords, cell.atom_coords(), a)
-        perm = np.argsort(owner, kind='stable').astype(np.int64)
-        counts = np.bincount(owner, minlength=cell.natm)
-        blk_off = np.append(0, np.cumsum(counts)).astype(np.int64)
-        nip_final = np.minimum(self.nip_per_atom(), counts).astype(np.int32)
-        nip = nip_final
-        if self.select == 'refined':
-            nip = np.minimum(np.ceil(self.nip_per_atom() * float(self.refine_over)).astype(np.int64), counts).astype(np.int32)
+        owner, perm, counts, blk_off, nip_final, nip = self._voronoi_budget()
         kmax = int(nip.max())
         t0 = self._tick('host_partition', t0)
         d_perm = be.to_device(perm)
@@ -445,6 +438,36 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         self._sel = dict(owner=owner, perm=perm, blk_off=blk_off, nip_final=nip_final, piv_h=piv_h, rank=rank, paneled=paneled,
                          rows_buf=rows_buf, rows_panel=rows_panel, spectral=spectral, rows_single=rows_single)
 
+    def _voronoi_budget(self, kfac=1):
+        """The Voronoi partition of the grid by atoms and the point budget per atom: (owner of every grid point, perm = the grid
+        points block by block, counts per block, blk_off, nip_final = c_isdf * nao_atom * kfac points per atom, nip = what the
+        per-atom selections pick: nip_final, or refine_over x as many CANDIDATES for select='refined' (_refine_pick))."""
+        cell = self.cell
+        a = np.asarray(cell.lattice_vectors(), dtype=float)
+        owner = self.backend.partition_by_atom(self.grids.coords, cell.atom_coords(), a)
+        perm = np.argsort(owner, kind='stable').astype(np.int64)
+        counts = np.bincount(owner, minlength=cell.natm)
+        blk_off = np.append(0, np.cumsum(counts)).astype(np.int64)
+        nip_final = np.minimum(self.nip_per_atom() * kfac, counts).astype(np.int32)
+        nip = nip_final
+        if self.select == 'refined':
+            nip = np.minimum(np.ceil(self.nip_per_atom() * kfac * float(self.refine_over)).astype(np.int64), counts).astype(np.int32)
+        return owner, perm, counts, blk_off, nip_final, nip
+
+    def _fit_preamble(self, orbitals, t0):
+        """Top of every pick-and-fit: forget the last fit and, for the (AO x occupied) pair space, put the occupied orbitals onto
+        this process's grid columns: psi = C_occ^T phi (fft_jk.py:235-238 forms the same rows, mo = ao C).  Returns t0."""
+        self._fit_state = None
+        self._W_omega = {}
+        self._V = None
+        self._psi = self._psiP = None
+        if orbitals is not None:
+            be = self.backend
+            self._psi = self._buffer('psi', (orbitals.shape[1], self.ao.shape[1]))
+            be.gemm_nn(be.to_device(np.ascontiguousarray(orbitals.T)), self.ao, self._psi)
+            t0 = self._tick('S2_occupied_on_grid', t0)
+        return t0
+
     def _pick_and_fit(self, orbitals=None):
         """S2 second stage + S3 + S4 + S5 from the candidates of _select_candidates: the final points ('refined': one pivoted
         Cholesky of the candidates' Gram matrix), the fit (block-Jacobi / Cholesky route, paneled when the rows exceed HBM) and W.
@@ -452,19 +475,9 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         (AO x occupied) pair space of that density (pair_space='occ')."""
         cell, be, sel = self.cell, self.backend, self._sel
         nao, G = self.ao.shape
-        t0 = time.perf_counter()
         perm, blk_off, piv_h, rank, owner = sel['perm'], sel['blk_off'], sel['piv_h'], sel['rank'], sel['owner']
         paneled, rows_buf, rows_panel = sel['paneled'], sel['rows_buf'], sel['rows_panel']
-        self._fit_state = None
-        self._W_omega = {}
-        self._V = None
-        self._psi = self._psiP = None
-        if orbitals is not None:
-            # psi = C_occ^T phi on the grid (fft_jk.py:235-238 forms the same rows, mo = ao C)
-            nocc = orbitals.shape[1]
-            self._psi = self._buffer('psi', (nocc, G))
-            be.gemm_nn(be.to_device(np.ascontiguousarray(orbitals.T)), self.ao, self._psi)
-            t0 = self._tick('S2_occupied_on_grid', t0)
+        t0 = self._fit_preamble(orbitals, time.perf_counter())
         clusters = self._bj_clusters()
         if self.select == 'refined':
             rank = self._refine_selection(perm, blk_off, piv_h, rank, int(sel['nip_final'].sum()), owner)
@@ -500,11 +513,12 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                 # S3c: no triangular solve over the grid.  theta <- Y' = D^-1 (aoP ao)^2
                 ip_off = self._bj_blocks(rank, clusters)
                 Afac, Dblk = self._bj_prepare(self.ao, 0, d_ip, ip_off, self.aoP, scratch=self.W)
-                self._bj_rows(self.aoP, 0, self.ao, G, Dblk, ip_off, theta)
+                self._bj_rows(self.aoP, self.ao, G, Dblk, ip_off, theta)
             else:
                 chol = self._buffer('factor', (P, P))
                 # forward solve only (Y = Lr^-1 B); the backward solve is applied to the (P, P) matrix below
-                self._chol_fit(d_ip, chol, theta, forward_only=not self._want_theta)
+                self.reg_used = self._chol_factor(self.ao, d_ip, chol)
+                self._chol_rows(chol, theta, forward_only=not self._want_theta)
             t0 = self._tick('S3_fit', t0)
             if route == 'blockjacobi':
                 self._fit_state = dict(kind='blockjacobi', theta=theta, Afac=Afac, Dblk=Dblk, ip_off=ip_off)
@@ -513,34 +527,36 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
             self._finish_W(self.W)
             t0 = self._tick('S4S5_coulomb_W', t0)
             self.fit_route_used = route
-            if route == 'blockjacobi' and self.fit_route == 'auto':
-                aoT = be.empty((nao, P))
-                be.gather_cols(self.ao, d_ip, aoT)
-                self.bj_check = self._bj_probe_mismatch(aoT, Afac, Dblk, ip_off, theta, G, None)
-                del aoT
-                t0 = self._tick('S5_route_check', t0)
-                if self.bj_check <= self.bj_check_tol:
+            probe = self._probe_setup(Afac, Dblk, ip_off, G, d_ip=d_ip, rows=theta) if route == 'blockjacobi' else None
+            if probe is not None:
+                passed, t0 = self._probe_verdict(probe, t0)
+                del probe
+                if passed:
                     break
-                warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e); '
-                              'rebuilding W with the Cholesky route' % (self.bj_check, self.bj_check_tol))
         self._keep_V_for_robust_k(t0)
         del theta
         self._built = True
         return self
 
-    def _chol_fit(self, d_ip, chol, theta, forward_only):
-        """S3b: chol <- Cholesky factor of the regularised Gram matrix of the points, theta <- Lr^-1 (rows) (and Lr^-T of that
-        unless forward_only), in the AO x AO or the (AO x occupied) pair space."""
+    def _chol_factor(self, ao, d_ip, chol):
+        """S3b, the P x P half: aoP <- ao[:, d_ip]^T, chol <- Cholesky factor of the regularised Gram matrix of the points, in the
+        AO x AO or the (AO x occupied) pair space.  Returns the regularisation used (reg_used)."""
+        be = self.backend
+        if self._psi is None:
+            return be.fit_prepare(ao, d_ip, self.reg_rel, self.aoP, chol)
+        be.gather_aoP(ao, d_ip, self.aoP)
+        be.gram_prod(self.aoP, self._psiP, chol)
+        be.shift_diag(chol, self.reg_rel)
+        return self.reg_rel + be.chol_inplace(chol, 0.0, scratch=self._buffer('W', tuple(chol.shape)))
+
+    def _chol_rows(self, chol, theta, forward_only):
+        """S3b, the half over the grid: theta <- Lr^-1 (pair rows) on this process's grid columns (and Lr^-T of that unless
+        forward_only)."""
         be = self.backend
         G = self.ao.shape[1]
         if self._psi is None:
-            self.reg_used = be.fit_prepare(self.ao, d_ip, self.reg_rel, self.aoP, chol)
             be.fit_apply(chol, self.aoP, self.ao, G, theta, forward_only=forward_only)
             return
-        be.gather_aoP(self.ao, d_ip, self.aoP)
-        be.gram_prod(self.aoP, self._psiP, chol)
-        be.shift_diag(chol, self.reg_rel)
-        self.reg_used = self.reg_rel + be.chol_inplace(chol, 0.0, scratch=self.W)
         be.pair_prod_rows(self.aoP, self._psiP, self.ao, self._psi, G, theta)
         be.factor_solve_half(chol, False, theta)
         if not forward_only:
@@ -613,35 +629,17 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         """S3c + S4 + S5 in the spectral form (fit_route.FitRouteMixin._finish_W_spectral): block-Jacobi route, the probe check
         alongside.  Returns False when the check fails (the caller then runs the classic build, which can fall back to the
         Cholesky route)."""
-        be = self.backend
-        P = len(self.ip)
-        nao, G = self.ao.shape
+        G = self.ao.shape[1]
         ip_off = self._bj_blocks(rank, clusters)
         Afac, Dblk = self._bj_prepare(self.ao, 0, d_ip, ip_off, self.aoP, scratch=self.W)
         self._fit_state = dict(kind='blockjacobi-spectral', Afac=Afac, Dblk=Dblk, ip_off=ip_off)
         t0 = self._tick('S3_fit', t0)
-        probe = None
-        if self.fit_route == 'auto':
-            aoT = be.empty((nao, P))
-            be.gather_cols(self.ao, d_ip, aoT)
-            T0, E = self._bj_probe_vectors(aoT, Afac, Dblk, ip_off)
-            del aoT
-            probe = (E, be.empty((E.shape[0], G)))
+        probe = self._probe_setup(Afac, Dblk, ip_off, G, d_ip=d_ip)
         self._finish_W_spectral(self.W, probe=probe)
         t0 = self._tick('S4S5_coulomb_W', t0)
         self.fit_route_used = 'blockjacobi'
         self.n_panels = 1
-        if probe is None:
-            return True
-        self.bj_check = self._bj_probe_energies(T0, probe[1], self.W, None)
-        self._tick('S5_route_check', t0)
-        tol = min(self.bj_check_tol, self.w_spectral_check_tol)
-        if self.bj_check <= tol:
-            return True
-        warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e) in the spectral build; '
-                      'rebuilding W the classic way' % (self.bj_check, tol))
-        self.w_spectral_fraction = None
-        return False
+        return probe is None or self._probe_verdict(probe, t0)[0]
 
     def _build_paneled(self, rank, clusters, d_ip, rows_buf, rows_panel, t0):
         """S3c + S4 + S5 with the fit rows produced panel by panel (more points than HBM holds rows for): block-Jacobi
@@ -649,9 +647,7 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         probe check runs alongside (its combination rows are accumulated panel by panel).  There is no Cholesky route to fall
         back to here (its rows depend on all earlier rows); a failed check rebuilds ONCE with pairs of clusters merged into
         one preconditioner block (a better-conditioned A', twice the block-solve flops) and raises if that fails too."""
-        be = self.backend
-        P = len(self.ip)
-        nao, G = self.ao.shape
+        G = self.ao.shape[1]
         group0 = int(self.bj_group)
         try:
             for attempt in range(2):
@@ -661,28 +657,17 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
                 rows = self._buffer('theta', (rows_buf, G))
                 self._fit_state = dict(kind='blockjacobi-paneled', rows=rows, panels=panels, Afac=Afac, Dblk=Dblk, ip_off=ip_off)
                 t0 = self._tick('S3_fit', t0)
-                probe = None
-                if self.fit_route == 'auto':
-                    aoT = be.empty((nao, P))
-                    be.gather_cols(self.ao, d_ip, aoT)
-                    T0, E = self._bj_probe_vectors(aoT, Afac, Dblk, ip_off)
-                    del aoT
-                    probe = (E, be.empty((E.shape[0], G)))
+                probe = self._probe_setup(Afac, Dblk, ip_off, G, d_ip=d_ip)
                 self._finish_W_paneled(self.W, probe=probe)
                 t0 = self._tick('S4S5_coulomb_W', t0)
                 self.fit_route_used = 'blockjacobi'
                 self.n_panels = len(panels)
                 if probe is None:
                     return
-                self.bj_check = self._bj_probe_energies(T0, probe[1], self.W, None)
-                t0 = self._tick('S5_route_check', t0)
-                if self.bj_check <= self.bj_check_tol:
+                passed, t0 = self._probe_verdict(probe, t0, warn=attempt == 0)
+                if passed:
                     return
-                if attempt == 0:
-                    warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e) in a paneled build, where '
-                                  'the Cholesky route is not available: rebuilding with pairs of clusters merged into one '
-                                  'preconditioner block' % (self.bj_check, self.bj_check_tol))
-                    self.bj_group = 2 * group0
+                self.bj_group = 2 * group0
             raise RuntimeError('ISDF: the paneled block-Jacobi build failed its probe check twice (mismatch %.2e > bj_check_tol = '
                                '%.2e): W would carry rounding noise of that relative size.  Use fewer points (c_isdf), more GPUs '
                                '(the rows then fit and the Cholesky route is available), or raise bj_check_tol knowingly.'
@@ -878,6 +863,8 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         them): W <- w conv(rows) rows^T, then the route's P x P finishing.  Uses the Coulomb kernel the backend is set to
         (plain, or range-separated for get_jk(omega=...): the fit itself does not depend on the kernel)."""
         be, st = self.backend, self._fit_state
+        if st.get('sharded'):
+            return self._finish_W_sharded(W)
         if st['kind'] == 'blockjacobi-paneled':
             return self._finish_W_paneled(W)
         if st['kind'] == 'blockjacobi-spectral':
@@ -912,9 +899,10 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
             cache[1][key] = pbc_tools.wigner_seitz_kernel(self.cell.lattice_vectors(), key)
         return cache[1][key]
 
-    def _W_kernel_variant(self, key, omega=None, cutoff=None, ws=None):
+    def _W_kernel_variant(self, key, omega=None, cutoff=None, ws=None, timing='S4S5_coulomb_W_variant'):
         """W rebuilt from the current fit with another Coulomb kernel (range-separated: omega; spherically truncated:
-        cutoff; Wigner-Seitz truncated: ws), cached under ``key`` until the next build.  The fit does not depend on the kernel."""
+        cutoff; Wigner-Seitz truncated: ws), cached under ``key`` until the next build.  The fit does not depend on the kernel.
+        The backend is back on the plain kernel afterwards."""
         be = self.backend
         if key not in self._W_omega:
             t0 = time.perf_counter()
@@ -923,13 +911,13 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
             be.set_coulomb_ws(ws)
             try:
                 W = be.empty(tuple(self.W.shape))
-                (self._finish_W_sharded if self._fit_state.get('sharded') else self._finish_W)(W)
+                self._finish_W(W)
             finally:
                 be.set_coulomb_omega(0.0)
                 be.set_coulomb_cutoff(0.0)
                 be.set_coulomb_ws(None)
             self._W_omega[key] = W
-            self._tick('S4S5_coulomb_W_variant', t0)
+            self._tick(timing, t0)
         return self._W_omega[key]
 
     def _get_jk_omega(self, dm, hermi, kpts, kpts_band, with_j, with_k, omega, exxdiv):
@@ -946,21 +934,12 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
             self.build()
         if with_k and self.pair_space == 'occ':
             self._ensure_fit(dm)
-        key = round(float(omega), 10)
-        be.set_coulomb_omega(omega)
+        W_plain, self.W = self.W, self._W_kernel_variant(round(float(omega), 10), omega=omega, timing='S4S5_coulomb_W_omega')
         try:
-            if key not in self._W_omega:
-                t0 = time.perf_counter()
-                W = be.empty(tuple(self.W.shape))
-                (self._finish_W_sharded if self._fit_state.get('sharded') else self._finish_W)(W)
-                self._W_omega[key] = W
-                self._tick('S4S5_coulomb_W_omega', t0)
-            W_plain, self.W = self.W, self._W_omega[key]
-            try:
-                return self.get_jk(dm, hermi, kpts, kpts_band, with_j, with_k, None, exxdiv)
-            finally:
-                self.W = W_plain
+            be.set_coulomb_omega(omega)                  # J, too, takes the range-separated kernel
+            return self.get_jk(dm, hermi, kpts, kpts_band, with_j, with_k, None, exxdiv)
         finally:
+            self.W = W_plain
             be.set_coulomb_omega(0.0)
 
     # ---- J / K ---------------------------------------------------------------------------------

@@ -100,7 +100,6 @@ class KPointMixin:
         G = int(np.prod(mesh))
         nao = cell.nao_nr()
         nh = nk * nao
-        a = np.asarray(cell.lattice_vectors(), dtype=float)
         coords = self.grids.coords
         rcut = gto.estimate_rcut_per_shell(cell)
         Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
@@ -127,14 +126,7 @@ class KPointMixin:
             sel['ip'] = be.to_host(piv[0, :int(rank[0])].contiguous()).astype(np.int64)
             sel['rank'] = rank
         else:
-            owner = be.partition_by_atom(coords, cell.atom_coords(), a)
-            perm = np.argsort(owner, kind='stable').astype(np.int64)
-            counts = np.bincount(owner, minlength=cell.natm)
-            blk_off = np.append(0, np.cumsum(counts)).astype(np.int64)
-            nip_final = np.minimum(self.nip_per_atom() * kfac, counts).astype(np.int32)
-            nip = nip_final
-            if self.select == 'refined':            # per-atom candidates, then one pivoted Cholesky among them (isdf._refine_pick)
-                nip = np.minimum(np.ceil(self.nip_per_atom() * kfac * float(self.refine_over)).astype(np.int64), counts).astype(np.int32)
+            owner, perm, counts, blk_off, nip_final, nip = self._voronoi_budget(kfac)
             kmax = int(nip.max())
             Xs = be.empty((2 * nh, G))
             be.gather_cols(X, be.to_device(perm), Xs)
@@ -255,7 +247,7 @@ class KPointMixin:
             if route == 'blockjacobi':
                 ip_off = self._bj_blocks(rank, clusters)
                 Afac, Dblk = self._bj_prepare(X, nh, ip_dev, ip_off, aoP_X)
-                self._bj_rows(aoP_X, nh, X, G, Dblk, ip_off, Y)
+                self._bj_rows(aoP_X, X, G, Dblk, ip_off, Y, nh=nh)
             elif Psi is not None:
                 # (AO x occupied) pairs: A_PP = Re[S_u conj(S_psi)] at the points, the rows B likewise, Y = L^-1 B
                 chol = self._buffer('factor', (P, P))

@@ -1,7 +1,6 @@
 """Grid-sharded multi-GPU build and J/K of ``isdf.ISDF``: one process per GPU, collectives through
 ``parallel.Comm`` (RCCL on GPUs, gloo in CPU tests).  Host orchestration only."""
 import time
-import warnings
 import numpy as np
 import torch
 from . import gto
@@ -57,7 +56,6 @@ class ShardedMixin:
         mesh = np.asarray(self.mesh, dtype=np.int32)
         G = int(np.prod(mesh))
         nao = cell.nao_nr()
-        a = np.asarray(cell.lattice_vectors(), dtype=float)
         coords = self.grids.coords
         rcut = gto.estimate_rcut_per_shell(cell)
         Ls = gto.get_lattice_Ls(cell, rcut=rcut.max())
@@ -73,14 +71,7 @@ class ShardedMixin:
         t0 = self._tick('S1_eval_ao', t0)
 
         # S2 selection on this rank's atom blocks
-        owner = be.partition_by_atom(coords, cell.atom_coords(), a)
-        perm = np.argsort(owner, kind='stable').astype(np.int64)
-        counts = np.bincount(owner, minlength=cell.natm)
-        blk_off = np.append(0, np.cumsum(counts)).astype(np.int64)
-        nip_final = np.minimum(self.nip_per_atom(), counts).astype(np.int32)
-        nip = nip_final
-        if self.select == 'refined':                      # the per-atom selections are candidates (isdf.ISDF._refine_pick)
-            nip = np.minimum(np.ceil(self.nip_per_atom() * float(self.refine_over)).astype(np.int64), counts).astype(np.int32)
+        owner, perm, counts, blk_off, nip_final, nip = self._voronoi_budget()
         mine = [b for b in range(cell.natm) if b % R == rk and nip[b] > 0]
         t0 = self._tick('host_partition', t0)
         my_ips = {}
@@ -126,15 +117,7 @@ class ShardedMixin:
         owner, merged, nip_final = sel['owner'], sel['merged'], sel['nip_final']
         nao, ng = self.ao.shape
         g0, g1 = self._slice
-        t0 = time.perf_counter()
-        self._fit_state = None
-        self._W_omega = {}
-        self._V = None
-        self._psi = self._psiP = None
-        if orbitals is not None:
-            self._psi = self._buffer('psi', (orbitals.shape[1], ng))
-            be.gemm_nn(be.to_device(np.ascontiguousarray(orbitals.T)), self.ao, self._psi)
-            t0 = self._tick('S2_occupied_on_grid', t0)
+        t0 = self._fit_preamble(orbitals, time.perf_counter())
         none = np.zeros(0, dtype=np.int64)                 # an atom that owns no grid points / no AOs selects nothing
         if self.select == 'refined':
             # phi at the candidates from the slice collocations (zero-padded all_reduce, 8 m N bytes); the pivoted
@@ -175,40 +158,29 @@ class ShardedMixin:
             plan = self._spectral_plan()
             if comm.agree_max(0.0 if plan is not None else 1.0) != 0.0:
                 plan = None
-        if plan is not None:
+
+        def bj_factors():
             Afac = self._buffer('factor', (P, P))
             Dblk = self._buffer('Dblk', (P, P))
 
             def root_factorise():
                 self._bj_prepare(aoP_T, 0, ar, ip_off, self.aoP, scratch=self._buffer('W', (P, P)))
                 return self.reg_used
-            reg = comm.run_on_root(root_factorise)
-            if comm.rank != 0:
-                be.gather_aoP(aoP_T, ar, self.aoP)
-                self._Dinv_key = None
-            comm.broadcast(Afac)
-            comm.broadcast(Dblk)
-            self.reg_used = comm.agree_max(reg or 0.0)
+            self._replicated_factors(root_factorise, aoP_T, ar, (Afac, Dblk))
+            return Afac, Dblk
+        if plan is not None:
+            Afac, Dblk = bj_factors()
             t0 = self._tick('S3_fit', t0)
             self._fit_state = dict(kind='blockjacobi-spectral', theta=None, sharded=True, Afac=Afac, Dblk=Dblk, ip_off=ip_off, chol=None)
-            probe = None
-            if self.fit_route == 'auto':
-                T0, E = self._bj_probe_vectors(aoP_T, Afac, Dblk, ip_off)
-                probe = (E, be.empty((E.shape[0], ng)))
+            probe = self._probe_setup(Afac, Dblk, ip_off, ng, aoT=aoP_T)
             self.W = self._buffer('W', (P, P))
             self._finish_W_sharded_spectral(self.W, plan, probe=probe)
             t0 = self._tick('S4S5_coulomb_W', t0)
             self.fit_route_used = 'blockjacobi'
             ok = True
             if probe is not None:
-                self.bj_check = comm.agree_max(self._bj_probe_energies(T0, probe[1], self.W, (g0, g1)))
-                t0 = self._tick('S5_route_check', t0)
-                tol = min(self.bj_check_tol, self.w_spectral_check_tol)
-                ok = self.bj_check <= tol
-                if not ok:
-                    warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e) in the spectral build; '
-                                  'rebuilding W the classic way' % (self.bj_check, tol))
-                    self.w_spectral_fraction = None
+                ok, t0 = self._probe_verdict(probe, t0)
+                del probe
             if ok:
                 del aoP_T
                 self._built = True
@@ -218,44 +190,13 @@ class ShardedMixin:
                                   'columns do not fit on rank %d; use more ranks or fewer points' % (P, ng, comm.rank))
         theta = self._buffer('theta', (P, ng))
         for route in routes:
-            # the P x P factorisations run on rank 0 and are broadcast (2 x 8 P^2 bytes): every rank then holds the
-            # same bits, and the shift ladders' decisions cannot diverge between ranks
             if route == 'blockjacobi':
-                Afac = self._buffer('factor', (P, P))
-                Dblk = self._buffer('Dblk', (P, P))
-                def root_factorise():
-                    self._bj_prepare(aoP_T, 0, ar, ip_off, self.aoP, scratch=self._buffer('W', (P, P)))
-                    return self.reg_used
-                reg = comm.run_on_root(root_factorise)
-                if comm.rank != 0:
-                    be.gather_aoP(aoP_T, ar, self.aoP)
-                    self._Dinv_key = None
-                comm.broadcast(Afac)
-                comm.broadcast(Dblk)
-                self.reg_used = comm.agree_max(reg or 0.0)
-                self._bj_rows(self.aoP, 0, self.ao, ng, Dblk, ip_off, theta)
+                Afac, Dblk = bj_factors()
+                self._bj_rows(self.aoP, self.ao, ng, Dblk, ip_off, theta)
             else:
                 chol = self._buffer('factor', (P, P))
-                if self._psi is None:
-                    reg = comm.run_on_root(lambda: be.fit_prepare(aoP_T, ar, self.reg_rel, self.aoP, chol))
-                else:
-                    def root_chol():
-                        be.gather_aoP(aoP_T, ar, self.aoP)
-                        be.gram_prod(self.aoP, self._psiP, chol)
-                        be.shift_diag(chol, self.reg_rel)
-                        return self.reg_rel + be.chol_inplace(chol, 0.0, scratch=self._buffer('W', (P, P)))
-                    reg = comm.run_on_root(root_chol)
-                if comm.rank != 0:
-                    be.gather_aoP(aoP_T, ar, self.aoP)
-                comm.broadcast(chol)
-                self.reg_used = comm.agree_max(reg or 0.0)
-                if self._psi is None:
-                    be.fit_apply(chol, self.aoP, self.ao, ng, theta, forward_only=not self._want_theta)
-                else:
-                    be.pair_prod_rows(self.aoP, self._psiP, self.ao, self._psi, ng, theta)
-                    be.factor_solve_half(chol, False, theta)
-                    if self._want_theta:
-                        be.factor_solve_half(chol, True, theta)
+                self._replicated_factors(lambda: self._chol_factor(aoP_T, ar, chol), aoP_T, ar, (chol,))
+                self._chol_rows(chol, theta, forward_only=not self._want_theta)
             t0 = self._tick('S3_fit', t0)
 
             self._fit_state = dict(kind=route if route == 'blockjacobi' else ('explicit' if self._want_theta else 'cholesky'),
@@ -266,18 +207,30 @@ class ShardedMixin:
             self._finish_W_sharded(self.W)
             t0 = self._tick('S4S5_coulomb_W', t0)
             self.fit_route_used = route
-            if route == 'blockjacobi' and self.fit_route == 'auto':
-                # replicated W, all-reduced probe energies; the max over ranks makes the decision identical everywhere
-                self.bj_check = comm.agree_max(self._bj_probe_mismatch(aoP_T, Afac, Dblk, ip_off, theta, ng, (g0, g1)))
-                t0 = self._tick('S5_route_check', t0)
-                if self.bj_check <= self.bj_check_tol:
+            probe = self._probe_setup(Afac, Dblk, ip_off, ng, aoT=aoP_T, rows=theta) if route == 'blockjacobi' else None
+            if probe is not None:
+                passed, t0 = self._probe_verdict(probe, t0)
+                del probe
+                if passed:
                     break
-                warnings.warn('ISDF: block-Jacobi fit route failed its probe check (mismatch %.2e > %.2e); '
-                              'rebuilding W with the Cholesky route' % (self.bj_check, self.bj_check_tol))
         self._keep_V_for_robust_k_sharded(t0)
         del theta, aoP_T
         self._built = True
         return self
+
+    def _replicated_factors(self, factorise, aoP_T, ar, factors):
+        """A P x P factorisation of the fit, replicated: factorise() runs on rank 0 (it fills self.aoP and the tensors in
+        `factors` and returns the regularisation it used) while the other ranks gather their aoP; the factors are broadcast
+        (8 P^2 bytes each) and reg_used agreed on - every rank then holds the same bits, and the shift ladders' decisions
+        cannot diverge between ranks."""
+        be, comm = self.backend, self.comm
+        reg = comm.run_on_root(factorise)
+        if comm.rank != 0:
+            be.gather_aoP(aoP_T, ar, self.aoP)
+            self._Dinv_key = None                        # (block factors may have been rewritten in the same buffers)
+        for f in factors:
+            comm.broadcast(f)
+        self.reg_used = comm.agree_max(reg or 0.0)
 
     def _slice_columns(self, idx, g0, g1, src=None):
         """phi (or the rows of ``src``, e.g. the occupied orbitals on the slice) at the grid points idx, (rows, len(idx)), on
@@ -294,6 +247,33 @@ class ShardedMixin:
             del loc
         comm.all_reduce_sum(out)
         return out
+
+    @staticmethod
+    def _views(flat, nrows, widths):
+        """Consecutive (nrows[q], widths[q]) views of a flat exchange buffer, one per rank."""
+        out, off = [], 0
+        for n, wd in zip(nrows, widths):
+            out.append(flat[off:off + n * wd].view(n, wd))
+            off += n * wd
+        return out
+
+    def _assemble_batch(self, send, pieces, full, slices):
+        """First all-to-all of a row pass: rank q receives the pieces send[q] (rows of ITS batch on the sender's grid slice) of
+        every rank into `pieces` and puts them side by side into `full` (its rows, G).  Returns the received pieces."""
+        recv = self._views(pieces, [full.shape[0]] * len(slices), [s1 - s0 for s0, s1 in slices])
+        self.comm.all_to_all(recv, send)
+        for (s0, s1), piece in zip(slices, recv):
+            full[:, s0:s1] = piece
+        return recv
+
+    def _scatter_batch(self, full, recv, back, nrow, slices):
+        """Second all-to-all of a row pass: the slice pieces of `full` go back the way they came (through the buffers `recv` of
+        _assemble_batch); returns, as views of `back`, rank q's batch (nrow[q] rows) on this rank's grid slice, for every q."""
+        for (s0, s1), piece in zip(slices, recv):
+            piece.copy_(full[:, s0:s1])
+        got = self._views(back, nrow, [self.ao.shape[1]] * len(nrow))
+        self.comm.all_to_all(got, recv)
+        return got
 
     def _finish_W_sharded(self, W):
         """S4 + S5 of the grid-sharded build for the fit held in self._fit_state (rows on this rank's grid slice + the
@@ -336,31 +316,16 @@ class ShardedMixin:
             bat = [(min(lo + t * nb, hi), min(lo + (t + 1) * nb, hi)) for lo, hi in rows]   # rows handled by rank q
             return bat, [hi - lo for lo, hi in bat]
 
-        def views(flat, nrow_of, width_of):
-            out, off = [], 0
-            for q in range(R):
-                n = nrow_of(q) * width_of(q)
-                out.append(flat[off:off + n].view(nrow_of(q), width_of(q)))
-                off += n
-            return out
-
         def exchange_and_convolve(t, slot):
             bat, nrow = batches(t)
             mine = nrow[rk]
             # all-to-all 1: send Theta[bat_q, S_r] to q; receive Theta[bat_r, S_q] from q
-            recv = views(pieces[slot], lambda q: mine, lambda q: slices[q][1] - slices[q][0])
-            comm.all_to_all(recv, [theta[lo:hi] for lo, hi in bat])
             rows_full = full[slot][:mine]
-            for (s0, s1), piece in zip(slices, recv):
-                rows_full[:, s0:s1] = piece
+            recv = self._assemble_batch([theta[lo:hi] for lo, hi in bat], pieces[slot], rows_full, slices)
             if mine:
                 be.coulomb_rows(rows_full, mesh, a, mine)
             # all-to-all 2: send V[bat_r, S_q] to q; receive V[bat_q, S_r] from q
-            for (s0, s1), piece in zip(slices, recv):
-                piece.copy_(rows_full[:, s0:s1])
-            got = views(recvV[slot], lambda q: nrow[q], lambda q: ng)
-            comm.all_to_all(got, recv)
-            return bat, nrow, got
+            return bat, nrow, self._scatter_batch(rows_full, recv, recvV[slot], nrow, slices)
 
         def products(bat, nrow, got):
             for q in range(R):
@@ -444,14 +409,6 @@ class ShardedMixin:
         full = be.empty((cap, G))
         Xb = be.empty((cap, ldx))
         recvX = be.empty((R * cap * max(kw, 1),))
-
-        def views(flat, nrow_of, width_of):
-            out, off = [], 0
-            for q in range(R):
-                n = nrow_of(q) * width_of(q)
-                out.append(flat[off:off + n].view(nrow_of(q), width_of(q)))
-                off += n
-            return out
         first = True
         for t in range(nsteps):
             bat = [p[t] if t < len(p) else (0, 0) for p in plans]
@@ -460,20 +417,17 @@ class ShardedMixin:
             for q, (lo, hi) in enumerate(bat):
                 blockrows = rows_loc[q * cap:q * cap + (hi - lo)]
                 if hi > lo:
-                    self._bj_rows_range(lo, hi, blockrows)
+                    self._bj_rows(self.aoP, self.ao, ng, st['Dblk'], st['ip_off'], blockrows, r0=lo, r1=hi)
                     if probe is not None:
                         be.rows_combine(probe[0][:, lo:hi], blockrows, probe[1], accumulate=not first)
                         first = False
                 send.append(blockrows)
             mine = nrow[rk]
-            recv = views(pieces, lambda q: mine, lambda q: slices[q][1] - slices[q][0])
-            comm.all_to_all(recv, send)
             rows_full = full[:mine]
-            for (s0, s1), piece in zip(slices, recv):
-                rows_full[:, s0:s1] = piece
+            self._assemble_batch(send, pieces, rows_full, slices)
             if mine:
                 be.spectral_rows(rows_full, mesh, plan['idx'], plan['scale'], Xb[:mine], batch=mine, **plan['lines_kw'])
-            got = views(recvX, lambda q: nrow[q], lambda q: kw)
+            got = self._views(recvX, nrow, [kw] * R)
             comm.all_to_all(got, [Xb[:mine, k0:k1].contiguous() for k0, k1 in ks])
             for q in range(R):
                 if nrow[q]:
@@ -508,23 +462,15 @@ class ShardedMixin:
         for t in range(nsteps):
             bat = [(min(lo + t * nb, hi), min(lo + (t + 1) * nb, hi)) for lo, hi in rows]
             nrow = [hi - lo for lo, hi in bat]
-            send = [theta[lo:hi] for lo, hi in bat]
-            recv = [be.empty((nrow[rk], s1 - s0)) for s0, s1 in slices]
-            comm.all_to_all(recv, send)
             full = be.empty((nrow[rk], G))
-            for (s0, s1), piece in zip(slices, recv):
-                full[:, s0:s1] = piece
-            del recv
+            recv = self._assemble_batch([theta[lo:hi] for lo, hi in bat], be.empty((nrow[rk] * G,)), full, slices)
             if nrow[rk]:
                 be.coulomb_rows(full, mesh, a, max(1, nrow[rk]))
-            send = [full[:, s0:s1].contiguous() for s0, s1 in slices]
-            recv = [be.empty((nrow[q], ng)) for q in range(R)]
-            comm.all_to_all(recv, send)
-            del full, send
+            got = self._scatter_batch(full, recv, be.empty((sum(nrow) * ng,)), nrow, slices)
             for q in range(R):
                 if nrow[q]:
-                    theta[bat[q][0]:bat[q][1]] = recv[q]          # rows bat_q were sent in this step's first all-to-all
-            del recv
+                    theta[bat[q][0]:bat[q][1]] = got[q]           # rows bat_q were sent in this step's first all-to-all
+            del full, recv, got
         self._V = theta
         self._fit_state = None
         self._tick('S5_conv_for_robust_k', t0)
