@@ -626,7 +626,14 @@ int isdf_hadamard_rows(isdf_handle h, double* d_X, int64_t ldx, const double* d_
  *                               LDA_C_VWN_RPA: A = 0.0310907, b = 13.0720, c = 42.7198, x0 = -0.409286; the reference's 'b3lyp').
  *                               LYP (libxc GGA_C_LYP) in the form of Miehlich, Savin, Stoll and Preuss.  Slater / VWN vanish for
  *                               rho <= 1e-24, B88 / LYP for rho <= 1e-14; a component with weight 0 is not evaluated
- *   isdf_gga_lyp_polarised:     spin-polarised LYP times ``weight``: rho_s at d_rho + s sstride, component c of grad rho_s at d_grad +
+ *   isdf_xc_fused_rsh:          isdf_xc_fused + c_b88_sr short-range B88 at ``omega`` >= 0 (the semilocal part of a range-separated
+ *                               hybrid; CAM-B3LYP: 0.35 B88 + 0.46 short-range B88 + 0.19 VWN fit V + 0.81 LYP, omega = 0.33).  Becke-88
+ *                               with the attenuation of Iikura, Tsuneda, Yanai and Hirao (JCP 115, 3540; libxc GGA_X_ITYH): per spin
+ *                               rho_s^(4/3) G(x) F(a), a = omega / (2 k), k = sqrt(9 pi / K) rho_s^(1/3), K = -2 G(x), F(a) = 1 - (8/3) a
+ *                               [sqrt(pi) erf(1/(2a)) + 2a (b - c)], b = exp(-1/(4a^2)) - 1, c = 2 a^2 b + 1/2; from a = 0.5 on F and
+ *                               F' are summed from the expansion in 1/a^2 (16 terms; the direct form cancels).  Same layout, strides
+ *                               and thresholds (short-range B88 vanishes for rho <= 1e-14); c_b88_sr = 0 is isdf_xc_fused bit for bit
+ *   isdf_gga_lyp_polarised:    spin-polarised LYP times ``weight``: rho_s at d_rho + s sstride, component c of grad rho_s at d_grad +
  *                               c gcstride + s sstride -> d_ec = weight e_c (energy density per VOLUME), d_vrho + s osstride (+)=
  *                               weight de/d rho_s, d_w + c wcstride + s osstride (+)= weight de/d(grad rho_s) = weight (2 vsigma_ss
  *                               grad rho_s + vsigma_ab grad rho_s'); accumulate = 1 adds to vrho and w (d_ec is always written).  A
@@ -661,6 +668,9 @@ int isdf_gga_b88(isdf_handle h, const double* d_rho, const double* d_grad, int64
                  double* d_vrho, double* d_w, int64_t wstride);
 int isdf_xc_fused(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double c_slater, double c_b88,
                   double c_vwn, int vwn_rpa, double c_lyp, double* d_exc, double* d_vrho, double* d_w, int64_t wstride);
+int isdf_xc_fused_rsh(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double c_slater, double c_b88,
+                      double c_vwn, int vwn_rpa, double c_lyp, double c_b88_sr, double omega, double* d_exc, double* d_vrho, double* d_w,
+                      int64_t wstride);
 int isdf_gga_lyp_polarised(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gcstride, int64_t sstride, int64_t n,
                            double weight, int accumulate, double* d_ec, double* d_vrho, double* d_w, int64_t wcstride,
                            int64_t osstride);

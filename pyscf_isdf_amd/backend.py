@@ -680,6 +680,14 @@ class HipBackend:
         self.handle.call('isdf_xc_fused', self._p(rho), self._p(grad), grad.stride(0), rho.numel(), cs, cb, cv, int(bool(vwn_rpa)), cl,
                          self._p(exc), self._p(vrho), self._p(w), w.stride(0))
 
+    def xc_fused_rsh(self, rho, grad, coeffs, vwn_rpa, c_b88_sr, omega, exc, vrho, w):
+        """xc_fused + c_b88_sr short-range (ITYH-attenuated) B88 at omega >= 0: the semilocal part of a range-separated hybrid."""
+        self._stream()
+        assert rho.is_contiguous() and exc.is_contiguous() and vrho.is_contiguous() and grad.stride(1) == 1 and w.stride(1) == 1
+        cs, cb, cv, cl = (float(x) for x in coeffs)
+        self.handle.call('isdf_xc_fused_rsh', self._p(rho), self._p(grad), grad.stride(0), rho.numel(), cs, cb, cv, int(bool(vwn_rpa)), cl,
+                         float(c_b88_sr), float(omega), self._p(exc), self._p(vrho), self._p(w), w.stride(0))
+
     def gga_lyp_polarised(self, rho, weight, ec, vxc, accumulate=False):
         """rho (4, 2, G) = (rho_s, grad rho_s) of the two spins -> ec (G,) = weight e_c (energy density) and
         vxc (4, 2, G) (+)= weight (de/d rho_s, de/d grad rho_s); rho / vxc may be strided views (points contiguous)."""

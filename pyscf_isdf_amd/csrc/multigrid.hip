@@ -197,26 +197,88 @@ __global__ void lda_vwn_add_kernel(const double* __restrict__ rho, int64_t n, do
 // beta = 0.0042; e(rho, grad rho) = 2 f(rho/2, |grad rho|/2).  Outputs: exc = e / rho, vrho = de/drho, and wfac with
 // w = de/d(grad rho) = 2 vsigma grad rho = wfac grad rho (what multiplies grad(phi_mu phi_nu) in the potential matrix).
 // rho <= 1e-14 gives zero.
+struct B88Parts { double r13, r43, x, Gx, Gp_over_x; };        // rho_s^(1/3), rho_s^(4/3), x, G(x), G'(x) / x (finite at x = 0)
+__device__ inline B88Parts b88_parts(double r, double g2) {
+  const double beta = 0.0042;
+  const double cx = 1.5 * cbrt(3.0 / (4.0 * 3.14159265358979323846));
+  const double rs = 0.5 * r;
+  const double r13 = cbrt(rs), r43 = rs * r13;
+  const double gs = 0.5 * sqrt(g2);
+  const double x = gs / r43;
+  const double as = asinh(x);
+  const double D = 1.0 + 6.0 * beta * x * as;
+  const double Dp = 6.0 * beta * (as + x / sqrt(1.0 + x * x));
+  const double Gx = -cx - beta * x * x / D;
+  const double Gp_over_x = -beta * (2.0 * D - x * Dp) / (D * D);
+  return B88Parts{r13, r43, x, Gx, Gp_over_x};
+}
+
 __device__ inline void b88_point(double r, double g2, double& e, double& vr, double& wfac) {
   e = 0.0;
   vr = 0.0;
   wfac = 0.0;
   if (r > 1e-14) {
-    const double beta = 0.0042;
-    const double cx = 1.5 * cbrt(3.0 / (4.0 * 3.14159265358979323846));
-    const double rs = 0.5 * r;
-    const double r13 = cbrt(rs), r43 = rs * r13;
-    const double gs = 0.5 * sqrt(g2);
-    const double x = gs / r43;
-    const double as = asinh(x);
-    const double D = 1.0 + 6.0 * beta * x * as;
-    const double Dp = 6.0 * beta * (as + x / sqrt(1.0 + x * x));
-    const double Gx = -cx - beta * x * x / D;
-    const double Gp_over_x = -beta * (2.0 * D - x * Dp) / (D * D);          // G'(x) / x, finite at x = 0
-    e = 2.0 * r43 * Gx / r;
-    vr = (4.0 / 3.0) * r13 * (Gx - x * x * Gp_over_x);
+    const B88Parts p = b88_parts(r, g2);
+    e = 2.0 * p.r43 * p.Gx / r;
+    vr = (4.0 / 3.0) * p.r13 * (p.Gx - p.x * p.x * p.Gp_over_x);
     // de/d|grad rho| = 2 f_gs / 2 = G'(x);  w = G'(x) grad rho / |grad rho| = (G'/x) grad rho / (2 rho_s^(4/3))
-    wfac = Gp_over_x / (2.0 * r43);
+    wfac = p.Gp_over_x / (2.0 * p.r43);
+  }
+}
+
+// Attenuation of the short-range exchange of Iikura, Tsuneda, Yanai and Hirao (JCP 115, 3540; libxc GGA_X_ITYH) and its derivative:
+//   F(a) = 1 - (8/3) a [sqrt(pi) erf(1/(2a)) + 2a (b - c)],  b = exp(-1/(4a^2)) - 1,  c = 2 a^2 b + 1/2,
+//   F'(a) = -(8/3) [sqrt(pi) erf(1/(2a)) + 2 a b - 16 a^3 b - 4 a].
+// The direct form cancels as a grows (F(1) = 0.027 = 1 - 0.973; at the 1e-14 density threshold a is in the thousands): from a = 0.5
+// on F is the expansion of the same expression in 1/(2a),
+//   F = sum_(n >= 1) (-1)^(n+1) 2 / ((n+1)! (2n+1) (n+2) 4^n) a^(-2n) = 1/(36 a^2) - 1/(960 a^4) + 1/(26880 a^6) - ...,
+// 16 terms (the 17th is 4e-18 of the first at a = 0.5).  In float64 against 30 digits on a from 1e-4 to 1e4: F 2.9e-15, F' 2.1e-15
+// relative, both at the direct form just below the switch.  a = 0 gives F = 1 (exp underflows, erf(inf) = 1).
+__device__ inline void ityh_attenuation(double a, double& F, double& dF) {
+  if (a < 0.5) {
+    const double rpi = 1.7724538509055160273;                              // sqrt(pi)
+    const double er = erf(1.0 / (2.0 * a));
+    const double b = exp(-1.0 / (4.0 * a * a)) - 1.0;
+    const double c = 2.0 * a * a * b + 0.5;
+    F = 1.0 - 8.0 * a * (rpi * er + 2.0 * a * (b - c)) / 3.0;
+    dF = -8.0 * (rpi * er + 2.0 * a * b - 16.0 * a * a * a * b - 4.0 * a) / 3.0;
+  } else {
+    constexpr int NT = 16;
+    constexpr double cn[NT] = {0.027777777777777776,    -0.0010416666666666667,  3.7202380952380956e-05,  -1.2056327160493827e-06,
+                               3.522952741702742e-08,   -9.315500038156288e-10,  2.2426203795561436e-11,  -4.94695671960914e-13,
+                               1.0059600984851122e-14,  -1.8961549475413822e-16, 3.3293690550475775e-18,  -5.469677733292448e-20,
+                               8.440860699525384e-22,   -1.2279269336594038e-23, 1.689273295831248e-25,   -2.2040181890054163e-27};
+    const double t = 1.0 / (a * a);
+    double f = 0.0, d = 0.0;
+#pragma unroll
+    for (int n = NT; n >= 1; --n) {                                        // Horner from the smallest term
+      f = (f + cn[n - 1]) * t;
+      d = (d - 2.0 * n * cn[n - 1]) * t;
+    }
+    F = f;
+    dF = d / a;
+  }
+}
+
+// Short-range Becke-88 of a spin-unpolarised density: per spin f = rho_s^(4/3) G(x) F(a), a = omega / (2 k),
+// k = sqrt(9 pi / K) rho_s^(1/3), K = -2 G(x) (the Fermi wave vector in the LDA limit); e = 2 f(rho/2, |grad rho|/2).  With
+// d ln a / d rho_s = -(1 + 2 x G'/G) / (3 rho_s) and d ln a / d g_s = G' / (2 G rho_s^(4/3)):
+//   vrho = rho_s^(1/3) [4 (G - x G') F - a F' (G + 2 x G')] / 3,   de/d|grad rho| = G' (F + a F'/2).
+// Outputs as b88_point; rho <= 1e-14 gives zero.
+__device__ inline void b88_sr_point(double r, double g2, double omega, double& e, double& vr, double& wfac) {
+  e = 0.0;
+  vr = 0.0;
+  wfac = 0.0;
+  if (r > 1e-14) {
+    const B88Parts p = b88_parts(r, g2);
+    const double k = sqrt(9.0 * 3.14159265358979323846 / (-2.0 * p.Gx)) * p.r13;
+    const double a = omega / (2.0 * k);
+    double F, dF;
+    ityh_attenuation(a, F, dF);
+    const double xGp = p.x * p.x * p.Gp_over_x;
+    e = 2.0 * p.r43 * p.Gx * F / r;
+    vr = p.r13 * (4.0 * (p.Gx - xGp) * F - a * dF * (p.Gx + 2.0 * xGp)) / 3.0;
+    wfac = p.Gp_over_x * (F + 0.5 * a * dF) / (2.0 * p.r43);
   }
 }
 
@@ -293,15 +355,11 @@ __device__ inline LypOut lyp_point(double ra, double rb, double saa, double sab,
 // exc per particle, vrho and w of  cs Slater + cb B88 + cv VWN (fit V, or the RPA fit with vwn_rpa) + cl LYP  of a spin-unpolarised
 // density in one pass: 4 planes in, 5 planes out.  A component with weight 0 is not evaluated.  Closed-shell LYP is lyp_point at
 // rho_a = rho_b = rho/2, sigma_aa = sigma_ab = sigma_bb = sigma/4: vrho = va, w = (vsaa + vsab + vsbb)/2 grad rho.
-__global__ void xc_fused_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n, double cs,
-                                double cb, double cv, int vwn_rpa, double cl, double* __restrict__ exc, double* __restrict__ vrho,
-                                double* __restrict__ w, int64_t wstride) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double r = rho[i];
-  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
-  const double g2 = gx * gx + gy * gy + gz * gz;
-  double e = 0.0, vr = 0.0, wfac = 0.0;
+__device__ inline void xc_fused_point(double r, double g2, double cs, double cb, double cv, int vwn_rpa, double cl, double& e, double& vr,
+                                      double& wfac) {
+  e = 0.0;
+  vr = 0.0;
+  wfac = 0.0;
   if (cs != 0.0) {
     double es, vs;
     slater_point(r, es, vs);
@@ -327,6 +385,42 @@ __global__ void xc_fused_kernel(const double* __restrict__ rho, const double* __
     e += cl * o.e / r;
     vr += cl * o.va;
     wfac += cl * 0.5 * (o.vsaa + o.vsab + o.vsbb);
+  }
+}
+
+__global__ void xc_fused_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n, double cs,
+                                double cb, double cv, int vwn_rpa, double cl, double* __restrict__ exc, double* __restrict__ vrho,
+                                double* __restrict__ w, int64_t wstride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
+  double e, vr, wfac;
+  xc_fused_point(rho[i], gx * gx + gy * gy + gz * gz, cs, cb, cv, vwn_rpa, cl, e, vr, wfac);
+  exc[i] = e;
+  vrho[i] = vr;
+  w[i] = wfac * gx;
+  w[wstride + i] = wfac * gy;
+  w[2 * wstride + i] = wfac * gz;
+}
+
+// The same sum + csr short-range B88 at ``omega`` (the semilocal part of a range-separated hybrid; CAM-B3LYP is 0.35 B88 + 0.46
+// short-range B88 + 0.19 VWN5 + 0.81 LYP at omega = 0.33): the fused point, then the one further term.  csr = 0 is xc_fused_kernel.
+__global__ void xc_fused_rsh_kernel(const double* __restrict__ rho, const double* __restrict__ grad, int64_t gstride, int64_t n,
+                                    double cs, double cb, double cv, int vwn_rpa, double cl, double csr, double omega,
+                                    double* __restrict__ exc, double* __restrict__ vrho, double* __restrict__ w, int64_t wstride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r = rho[i];
+  const double gx = grad[i], gy = grad[gstride + i], gz = grad[2 * gstride + i];
+  const double g2 = gx * gx + gy * gy + gz * gz;
+  double e, vr, wfac;
+  xc_fused_point(r, g2, cs, cb, cv, vwn_rpa, cl, e, vr, wfac);
+  if (csr != 0.0) {
+    double eb, vb, wb;
+    b88_sr_point(r, g2, omega, eb, vb, wb);
+    e += csr * eb;
+    vr += csr * vb;
+    wfac += csr * wb;
   }
   exc[i] = e;
   vrho[i] = vr;
@@ -668,6 +762,19 @@ extern "C" int isdf_xc_fused(isdf_handle h, const double* d_rho, const double* d
   ProfScope ps(h, "xc_fused_kernel[byte]", 72.0 * (double)n);
   hipLaunchKernelGGL(xc_fused_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, d_grad, gstride, n, c_slater, c_b88,
                      c_vwn, vwn_rpa, c_lyp, d_exc, d_vrho, d_w, wstride);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_xc_fused_rsh(isdf_handle h, const double* d_rho, const double* d_grad, int64_t gstride, int64_t n, double c_slater,
+                                 double c_b88, double c_vwn, int vwn_rpa, double c_lyp, double c_b88_sr, double omega, double* d_exc,
+                                 double* d_vrho, double* d_w, int64_t wstride) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, d_rho && d_grad && d_exc && d_vrho && d_w && n > 0 && gstride >= n && wstride >= n && (vwn_rpa == 0 || vwn_rpa == 1) &&
+                   omega >= 0.0 && std::isfinite(omega));
+  ProfScope ps(h, "xc_fused_rsh_kernel[byte]", 72.0 * (double)n);
+  hipLaunchKernelGGL(xc_fused_rsh_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_rho, d_grad, gstride, n, c_slater,
+                     c_b88, c_vwn, vwn_rpa, c_lyp, c_b88_sr, omega, d_exc, d_vrho, d_w, wstride);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }

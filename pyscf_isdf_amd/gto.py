@@ -501,14 +501,26 @@ def super_cell(cell, ncopy, mesh=None):
                 precision=cell.precision, pseudo=cell.pseudo)
 
 
-def madelung(cell, nk=(1, 1, 1)):
+def madelung(cell, nk=(1, 1, 1), omega=0.0):
     """Madelung constant of the (nk-fold) cell: -2 x the Ewald energy of one unit point charge with a
     neutralising background (pyscf/pbc/tools/pbc.py:483-493, Ewald sum of pyscf/pbc/gto/cell.py:692-768).
-    Used for the G=0 exchange correction exxdiv='ewald' (pyscf/pbc/df/df_jk.py:1446-1465)."""
-    from scipy.special import erfc
+    Used for the G=0 exchange correction exxdiv='ewald' (pyscf/pbc/df/df_jk.py:1446-1465).
+    omega > 0: the probe-charge constant of the attenuated interaction erf(omega r)/r (pbc.py:495-511),
+    xi = 2 omega / sqrt(pi) - 1/V sum_(G != 0) 4 pi / G^2 exp(-G^2 / 4 omega^2); no Ewald split is needed, the
+    kernel decays by itself, and the sum is carried to where the exponential is below 1e-18."""
     a = np.einsum('xi,x->xi', cell.lattice_vectors(), np.asarray(nk, dtype=float))
     vol = abs(np.linalg.det(a))
     b = 2 * np.pi * np.linalg.inv(a.T)
+    if omega != 0:
+        if not omega > 0:
+            raise ValueError('madelung: omega = %r (the long-range interaction erf(omega r)/r has omega > 0)' % (omega,))
+        gmax = 2 * omega * np.sqrt(-np.log(1e-18))
+        ng = np.ceil(gmax * np.linalg.norm(a, axis=1) / (2 * np.pi)).astype(int) + 1
+        Gs = cartesian_prod([np.arange(-n, n + 1) for n in ng]).dot(b)
+        g2 = np.einsum('gi,gi->g', Gs, Gs)
+        g2 = np.sort(g2[(g2 > 1e-12) & (g2 < gmax * gmax)])[::-1]            # smallest terms first
+        return 2 * omega / np.sqrt(np.pi) - (4 * np.pi / vol) * (np.exp(-g2 / (4 * omega * omega)) / g2).sum()
+    from scipy.special import erfc
     eta = np.sqrt(np.pi) / vol ** (1. / 3)
     # real-space and reciprocal-space cutoffs for ~1e-14 relative truncation
     rmax = 6.5 / eta

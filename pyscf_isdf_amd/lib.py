@@ -120,6 +120,7 @@ SIGNATURES = {
     'isdf_lda_vwn_add': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     'isdf_gga_b88': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64]),
     'isdf_xc_fused': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_dbl, c_dbl, c_int, c_dbl, c_vp, c_vp, c_vp, c_i64]),
+    'isdf_xc_fused_rsh': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_dbl, c_dbl, c_dbl, c_int, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_i64]),
     'isdf_gga_lyp_polarised': (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_dbl, c_int, c_vp, c_vp, c_vp, c_i64, c_i64]),
     'isdf_lda_exchange_fxc': (c_int, [c_vp, c_vp, c_i64, c_vp]),
     'isdf_lda_vwn_fxc_add': (c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -25,16 +25,19 @@ What differs from the reference, by design for the GPU:
 Everything numerical runs in libmi355_isdf.so (multigrid.hip, eval_ao.hip, gemm_f64.hip); this file plans the levels and
 scatters the small level matrices into J on the host.
 
-Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, hybrid_coeff, nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc,
-cache_xc_kernel1, _gen_rhf_response, _gen_uhf_response, multi_grids_tasks, multigrid_fftdf - the names of
-pyscf/pbc/dft/multigrid/__init__.py and multigrid.py - and the XC nuclear forces get_vxc_e1, xc_nuc_grad, xc_nuc_grad_uks (xc_grad.py).
+Surface: MultiGridFFTDF (get_jk, get_j_kpts, get_rho, tasks), nr_rks, nr_uks, hybrid_coeff, rsh_and_hybrid_coeff, hybrid_k,
+nr_rks_fxc, nr_rks_fxc_st, nr_uks_fxc, cache_xc_kernel1, _gen_rhf_response, _gen_uhf_response, multi_grids_tasks,
+multigrid_fftdf - the names of pyscf/pbc/dft/multigrid/__init__.py and multigrid.py - and the XC nuclear forces get_vxc_e1,
+xc_nuc_grad, xc_nuc_grad_uks (xc_grad.py).
 
 K is the ISDF exchange of the parent class (``MultiGridFFTDF(ISDF)``): hybrid functionals get J/XC from here and K from the
 interpolation, which is the pairing SURVEY section 8 f-3 names.  XC: the Slater exchange ('lda,') and Becke's 1988 exchange
 ('b88,', a GGA; Gamma point and k-points) in closed form - libxc is not part of this tree; both are pinned by the reference's SCF energies.
 LYP correlation completes them to BLYP and to the semilocal part of the B3LYP family (_XC_TABLE; one fused launch per density,
 isdf_xc_fused; open shell: isdf_gga_lyp_polarised), pinned by the reference's BLYP constants; hybrid_coeff tells the caller how much
-of the ISDF K to add.  k-points: the same two passes on the periodic parts u_k, real and imaginary planes stacked so that the complex
+of the ISDF K to add.  CAM-B3LYP adds the short-range B88 exchange (the ITYH attenuation; isdf_xc_fused_rsh, closed shell), pinned by
+the reference's CAM-B3LYP energies; hybrid_k combines the ISDF K with the long-range K of ISDF.get_jk(omega=...) for it.
+k-points: the same two passes on the periodic parts u_k, real and imaginary planes stacked so that the complex
 contractions are the Gamma point's real rectangular ones (get_j_kpts, nr_rks with kpts).
 """
 import copy
@@ -281,7 +284,26 @@ def _xc_rows():
             (('B3LYP', 'B3LYPG'), (0.08, 0.72, 0.19, 'RPA', 0.81, 0.2))):
         for c in codes:
             rows[c] = w
+    # libxc.py:758,1279 (HYB_GGA_XC_CAM_B3LYP): 0.35 B88 + 0.46 short-range B88 + 0.19 VWN fit V + 0.81 LYP; exact exchange
+    # 0.19 K + (0.65 - 0.19) K_LR(omega = 0.33).  The fit and the weights are pinned by the reference's energies (tests/test_rsh.py)
+    for c in ('CAMB3LYP', 'CAM-B3LYP', 'CAM_B3LYP', 'HYB_GGA_XC_CAM_B3LYP'):
+        rows[c] = _RshRow((0.0, 0.35, 0.19, 'V', 0.81, 0.19), c_b88_sr=0.46, omega=0.33, alpha=0.65)
     return rows
+
+
+class _RshRow(tuple):
+    """A row of _XC_TABLE of a range-separated hybrid: the same 6-tuple (hyb: the exact exchange at every range) with the weight of the
+    short-range B88 (the ITYH attenuation at ``omega``) and ``alpha``, the exact exchange at long range."""
+
+    def __new__(cls, row, c_b88_sr, omega, alpha):
+        self = tuple.__new__(cls, row)
+        self.c_b88_sr, self.omega, self.alpha = float(c_b88_sr), float(omega), float(alpha)
+        return self
+
+    def with_omega(self, omega):
+        if not omega > 0:
+            raise ValueError('omega = %r: the range-separation parameter is positive' % (omega,))
+        return _RshRow(tuple(self), self.c_b88_sr, omega, self.alpha)
 
 
 _XC_TABLE = _xc_rows()
@@ -298,14 +320,58 @@ def _functional(xc_code):
     w = _XC_TABLE.get(str(xc_code).replace(' ', '').upper())
     if w is None:
         raise NotImplementedError("xc=%r: 'lda,' (Slater exchange), 'lda,vwn' (+ VWN5 correlation), 'b88,' (Becke-88 exchange), 'blyp' / "
-                                  "'b88,lyp', ',lyp', 'b3lyp5' and 'b3lyp' / 'b3lypg' are implemented (no libxc in this tree)" % (xc_code,))
+                                  "'b88,lyp', ',lyp', 'b3lyp5', 'b3lyp' / 'b3lypg' and 'camb3lyp' are implemented (no libxc in this tree)"
+                                  % (xc_code,))
     return w
 
 
+def _functional_at(xc_code, omega):
+    """_functional with the caller's ``omega`` in place of the functional's own (the reference's mf.omega); None keeps it.  An omega
+    for a functional without range separation is a ValueError."""
+    fn = _functional(xc_code)
+    if omega is None:
+        return fn
+    if not isinstance(fn, _RshRow):
+        raise ValueError('omega = %r: xc=%r is not range-separated' % (omega, xc_code))
+    return fn.with_omega(float(omega))
+
+
 def hybrid_coeff(xc_code):
-    """Fraction of exact exchange of ``xc_code``: 0.2 for the B3LYP family, 0.0 for the other implemented functionals.  nr_rks
-    returns the semilocal part only, as the reference's does; the caller adds -hyb/2 K (closed shell) from ISDF.get_jk."""
+    """Fraction of exact exchange of ``xc_code``: 0.2 for the B3LYP family, 0.19 for CAM-B3LYP (at every range; rsh_and_hybrid_coeff
+    has the long-range part), 0.0 for the other implemented functionals.  nr_rks returns the semilocal part only, as the reference's
+    does; the caller adds -1/2 hybrid_k (closed shell)."""
     return _functional(xc_code)[5]
+
+
+def rsh_and_hybrid_coeff(xc_code):
+    """(omega, alpha, hyb) as numint.rsh_and_hybrid_coeff (numint.py:2708-2727): exact exchange hyb K + (alpha - hyb) K_LR(omega).
+    CAM-B3LYP: (0.33, 0.65, 0.19); every other code (0, 0, hybrid_coeff)."""
+    fn = _functional(xc_code)
+    if isinstance(fn, _RshRow):
+        return fn.omega, fn.alpha, fn[5]
+    return 0.0, 0.0, fn[5]
+
+
+def hybrid_k(mydf, xc_code, dm, omega=None, exxdiv='ewald'):
+    """The exchange matrix a hybrid Fock build subtracts half of (closed shell): hyb K + (alpha - hyb) K_LR(omega) of
+    pbc/dft/rks.py:108-113, K from mydf.get_jk(exxdiv=exxdiv) and K_LR from mydf.get_jk(omega=omega) - the ISDF exchange with the
+    plain and the attenuated kernel.  With exxdiv='ewald' the long-range part carries the probe-charge correction of its own
+    interaction, madelung(cell, omega=omega) S D S (pbc.py:495-511), S = mydf.overlap().  ``omega`` None: the functional's own.  A
+    global hybrid gives hyb K, a functional without exact exchange zeros.  Gamma point, one process."""
+    fn = _functional_at(xc_code, omega)
+    mydf._ppg_refuse(None, 'hybrid_k')
+    hyb = fn[5]
+    dm_in = np.asarray(dm)
+    vk = np.zeros(dm_in.shape)
+    if hyb != 0:
+        vk = vk + hyb * mydf.get_jk(dm, with_j=False, exxdiv=exxdiv)[1]
+    if isinstance(fn, _RshRow) and fn.alpha != hyb:
+        klr = mydf.get_jk(dm, with_j=False, omega=fn.omega, exxdiv='None')[1]
+        if exxdiv == 'ewald':
+            S = mydf.backend.to_host(mydf.overlap())
+            klr = klr + gto.madelung(mydf.cell, omega=fn.omega) * np.einsum('ij,...jk,kl->...il', S, dm_in.real, S)
+        vk = vk + (fn.alpha - hyb) * klr
+    return vk
 
 
 class _Planes:
@@ -616,14 +682,15 @@ def _kpts_or_gamma(mydf, kpts, kpts_band):
     return None if mydf._is_gamma(kpts) and mydf._is_gamma(kpts_band) else kpts
 
 
-def nr_rks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None):
+def nr_rks(mydf, xc_code, dm_kpts, hermi=1, kpts=None, kpts_band=None, with_j=False, return_j=False, verbose=None, omega=None):
     """XC energy and potential matrix of a closed-shell density through the level ladder (multigrid.py:1046-1150): the functionals
     of _XC_TABLE - Slater exchange (with or without VWN5 correlation), Becke-88 exchange, BLYP, LYP alone and the semilocal part of
-    the B3LYP family (hybrid_coeff gives the exact-exchange fraction the caller adds); Gamma point (real matrices) or k-points
+    the B3LYP family and of CAM-B3LYP (hybrid_k gives the exact exchange the caller adds); Gamma point (real matrices) or k-points
     (dm (nk, nao, nao) or (nset, nk, nao, nao), complex result on the k-points or on kpts_band).  Returns (nelec, exc, veff) with
     veff tagged ecoul / exc / vj / vk like the reference's; with_j adds the Coulomb potential to veff before the integration pass
-    (one pass for J + XC)."""
-    fn = _functional(xc_code)
+    (one pass for J + XC).  ``omega`` replaces the range-separation parameter of a range-separated functional in the attenuation
+    of its short-range exchange (the reference's mf.omega); for any other functional it is a ValueError."""
+    fn = _functional_at(xc_code, omega)
     return _nr_ks(mydf, fn, isinstance(xc_code, (tuple, list)), dm_kpts, _kpts_or_gamma(mydf, kpts, kpts_band), kpts_band, with_j,
                   return_j, False)
 
@@ -648,10 +715,13 @@ def _xc_dispatch(be, fn, raw, spin):
     """Which kernels evaluate the functional ``fn`` (a row of _XC_TABLE; ``raw``: caller's weights) - shared by _nr_ks and the
     nuclear forces of xc_grad: (ncomp, pair_lyp, per_channel, channel).  ncomp: 1 without gradients, 4 with; channel(rho (ncomp, G),
     exc (G,), vxc (ncomp, G)) launches the one kernel of a density - isdf_lda_exchange [+ isdf_lda_vwn_add], isdf_gga_b88 for Becke's
-    exchange alone, isdf_xc_fused for every other weighted sum; ``spin``: the channel is the exchange part alone (at 2 rho_s), pair_lyp
-    says that LYP of (rho_a, rho_b) together follows (isdf_gga_lyp_polarised), per_channel that there is a channel part at all."""
+    exchange alone, isdf_xc_fused for every other weighted sum, isdf_xc_fused_rsh for one with a short-range B88 weight; ``spin``: the
+    channel is the exchange part alone (at 2 rho_s), pair_lyp says that LYP of (rho_a, rho_b) together follows
+    (isdf_gga_lyp_polarised), per_channel that there is a channel part at all.  (No range-separated functional reaches this with
+    ``spin``: the only one carries VWN, which nr_uks and xc_nuc_grad_uks refuse first.)"""
     cs, cb, cv, fit, cl, _ = fn
-    ncomp = 4 if (cb != 0 or cl != 0 or raw) else 1
+    csr, omega = (fn.c_b88_sr, fn.omega) if isinstance(fn, _RshRow) else (0.0, 0.0)
+    ncomp = 4 if (cb != 0 or cl != 0 or csr != 0 or raw) else 1
     pair_lyp = spin and cl != 0                                              # LYP of (rho_a, rho_b) together
     if spin:
         cv, cl = 0.0, 0.0                                                    # per channel: the exchange part alone
@@ -662,6 +732,8 @@ def _xc_dispatch(be, fn, raw, spin):
             be.lda_exchange(rho[0], exc, vxc[0])
             if cv != 0:
                 be.lda_vwn_add(rho[0], exc, vxc[0])
+        elif csr != 0:
+            be.xc_fused_rsh(rho[0], rho[1:], (cs, cb, cv, cl), fit == 'RPA', csr, omega, exc, vxc[0], vxc[1:])
         elif (cs, cb, cv, cl) == (0.0, 1.0, 0.0, 0.0) and not raw:
             be.gga_b88(rho[0], rho[1:], exc, vxc[0], vxc[1:])
         else:

@@ -127,13 +127,13 @@ def _forces(mydf, fn, raw, dms, spin):
     return f
 
 
-def xc_nuc_grad(mydf, xc_code, dm, kpts=None):
+def xc_nuc_grad(mydf, xc_code, dm, kpts=None, omega=None):
     """dE_xc/dR_A at fixed D for the closed-shell XC energy of nr_rks(mydf, xc_code, dm), the AOs moving with their atoms: (natm, 3),
     or (nset, natm, 3) for a stack, without the (3, nao, nao) matrix of get_vxc_e1.  Exact for every code of _XC_TABLE on the dense
     mesh (the GGAs through the AO second derivatives); no grid response (the uniform mesh does not move with the atoms).  dm is real
-    (max|Im| above 1e-12 raises ValueError); only its symmetric part contributes."""
+    (max|Im| above 1e-12 raises ValueError); only its symmetric part contributes.  ``omega`` as in nr_rks."""
     mg = _mg()
-    fn = mg._functional(xc_code)
+    fn = mg._functional_at(xc_code, omega)
     _refuse(mydf, kpts, 'xc_nuc_grad')
     dms, single = mydf._ppg_dms(dm)
     f = _forces(mydf, fn, isinstance(xc_code, (tuple, list)), dms, False)
@@ -155,13 +155,13 @@ def xc_nuc_grad_uks(mydf, xc_code, dm_ab):
     return _forces(mydf, fn, isinstance(xc_code, (tuple, list)), dms, True).sum(axis=0)
 
 
-def get_vxc_e1(mydf, xc_code, dm, kpts=None):
+def get_vxc_e1(mydf, xc_code, dm, kpts=None, omega=None):
     """vxc_e1[x, mu, nu] = - wq sum_g [d_x phi_mu Z_nu + G_(x mu) phi_nu], the derivative on the bra: the reference's get_vxc
     (pyscf/pbc/grad/krks.py:68-112, -vmat) at the Gamma point for the potential of the closed-shell density of dm.  (3, nao, nao)
     for one matrix, (3, nset, nao, nao) for a stack - the shapes of get_j_e1.  For a symmetric dm,
-    xc_nuc_grad(dm)[A] = 2 sum_(mu in A) sum_nu vxc_e1[:, mu, nu] dm_(nu mu)."""
+    xc_nuc_grad(dm)[A] = 2 sum_(mu in A) sum_nu vxc_e1[:, mu, nu] dm_(nu mu).  ``omega`` as in nr_rks."""
     mg = _mg()
-    fn = mg._functional(xc_code)
+    fn = mg._functional_at(xc_code, omega)
     _refuse(mydf, kpts, 'get_vxc_e1')
     dms, single = mydf._ppg_dms(dm)
     t0 = time.perf_counter()
