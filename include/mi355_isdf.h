@@ -699,6 +699,21 @@ int isdf_pack_table_pm(isdf_handle h, const double* d_tab, const int32_t mesh[3]
 int isdf_herm_kscale_nt(isdf_handle h, int M, int N, int64_t K, double alpha, const double* d_A, int64_t lda, const double* d_B,
                         int64_t ldb, const double* d_s, const double* d_a, double beta, double* d_Cre, double* d_Cim, int64_t ldc);
 
+/* Opposite-spin MP2 from the THC form of the Gamma-point factors (host loop in pyscf_isdf_amd/thc_mp2.py):
+ * per Laplace point E_t = Tr[(W A)^2], A = (Xo diag(so) Xo^T) o (Xv diag(sv) Xv^T), W A by isdf_gemm_nt (A is symmetric to the bit).
+ *   isdf_thc_pair: A (P, lda) <- (sum_i Xo[p,i] so[i] Xo[q,i]) (sum_a Xv[p,a] sv[a] Xv[q,a]); Xo (P, ldo), Xv (P, ldv) row-major with
+ *                  the orbital index contiguous, ldo >= no, ldv >= nv, lda >= P (else ISDF_ERR_ARG).  One pass: each 128 x 128 tile
+ *                  keeps both sums in v_mfma_f64_16x16x4_f64 accumulators and stores their product; neither factor is stored.  The
+ *                  scale is applied to one operand on its way to LDS, K tails are zero-filled there.  Only the lower triangle is
+ *                  computed and every value is stored at (p, q) and (q, p): A[p,q] and A[q,p] are the same bits.  Any leading
+ *                  dimensions and alignment (16-byte aligned rows of Xo and Xv take the vector loads); columns >= P of A are not
+ *                  touched
+ *   isdf_trace_sq: *result (host) = sum_ij B_ij B_ji of B (n, ldb), ldb >= n; per-workgroup partials of 32 x 32 tile pairs, then
+ *                  one fixed-order sum; synchronises; two calls on the same data return the same bits */
+int isdf_thc_pair(isdf_handle h, int P, const double* d_Xo, int64_t ldo, int no, const double* d_so, const double* d_Xv, int64_t ldv,
+                  int nv, const double* d_sv, double* d_A, int64_t lda);
+int isdf_trace_sq(isdf_handle h, int n, const double* d_B, int64_t ldb, double* result);
+
 /* Dense helper behind S5/S6 (exposed for tests and micro-benchmarks):
  *   C (M, ldc) = alpha * A (M, lda) * (B (N, ldb) .* kscale[None, :])^T + beta * C,
  * K contiguous in both operands (the W = V Theta^T / vj = ao (v.ao)^T shape); d_kscale may be NULL.

@@ -586,6 +586,27 @@ class HipBackend:
         self.handle.call('isdf_gemm_nn_had', M, N, K, float(alpha), self._p(A), A.stride(0), self._p(H), H.stride(0), self._p(B),
                          B.stride(0), float(beta), self._p(C), C.stride(0))
 
+    # ---- opposite-spin MP2 from the THC form of the factors (thc_mp2.py) --------------------------------
+    def thc_pair(self, Xo, so, Xv, sv, A):
+        """A (P, P) <- (Xo diag(so) Xo^T) .* (Xv diag(sv) Xv^T) in one pass, symmetric to the bit; Xo (P, no), Xv (P, nv) with the
+        orbital index contiguous (include/mi355_isdf.h isdf_thc_pair)."""
+        self._stream()
+        P, no = Xo.shape
+        nv = Xv.shape[1]
+        assert Xv.shape[0] == P and tuple(A.shape) == (P, P) and so.numel() == no and sv.numel() == nv
+        assert Xo.stride(1) == 1 and Xv.stride(1) == 1 and A.stride(1) == 1 and so.is_contiguous() and sv.is_contiguous()
+        self.handle.call('isdf_thc_pair', P, self._p(Xo), Xo.stride(0), no, self._p(so), self._p(Xv), Xv.stride(0), nv,
+                         self._p(sv), self._p(A), A.stride(0))
+
+    def trace_sq(self, B):
+        """sum_ij B_ij B_ji = Tr[B^2] of a square B, fixed summation order (include/mi355_isdf.h isdf_trace_sq); synchronises."""
+        self._stream()
+        n = B.shape[0]
+        assert tuple(B.shape) == (n, n) and B.stride(1) == 1
+        out = ctypes.c_double(0.0)
+        self.handle.call('isdf_trace_sq', n, self._p(B), B.stride(0), ctypes.byref(out))
+        return out.value
+
     # ---- k-point M^q from the packed half spectra of the fit rows (DESIGN.md section 6b) ------------------------------------
     def pack_table_pm(self, table, mesh, idx, scale, s, a):
         """s, a (ldx,) <- scale (c(G_t) +- (m_t - 1) c(-G_t)) on the packed points idx (int32 half-spectrum indices), each value on

@@ -33,6 +33,7 @@
 //    and of storing it, and a new user writes a kernel that decodes its unit, calls it and stores.  The NN form keeps a main
 //    loop of its own: as a B-operand policy of tile_256x128 it compiled to another loop than the one measured.
 #include "common.h"
+#include "gemm_tile.h"
 #include <cstdlib>
 
 int gemm_rm(isdf_handle h, char opA, char opB, int64_t M, int64_t N, int64_t K, double alpha,
@@ -50,8 +51,6 @@ int gemm_rm(isdf_handle h, char opA, char opB, int64_t M, int64_t N, int64_t K, 
 }
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 16;
 constexpr int LDT = 17;          // doubles per LDS row: 16 + 1 pad (136 B = 34 banks): the fragment reads (ds_read2_b64,
@@ -72,44 +71,7 @@ struct GemmArgs {
   int direct;
 };
 
-// ---- what the kernels share: unit decode, accumulator store, issue order ------------------------------------------------------------
-// XCD-aware unit id: hardware deals consecutive block ids round-robin over 8 XCDs; give each XCD a
-// contiguous range of units so that neighbours (which share operand panels) share an L2.  Units past the caller's count are
-// the padding of the last round.
-__device__ __forceinline__ int64_t xcd_unit(int64_t nunits_pad) {
-  const int64_t bid = blockIdx.x;
-  const int64_t per_xcd = nunits_pad / 8;
-  return (bid % 8) * per_xcd + bid / 8;
-}
-
-struct Tile { int tm, tn, slab; };      // slab stays 0 where K is not cut (NN)
-struct KRange { int64_t k0, k1; };
-
-// slab-major units, row tile fastest
-__device__ __forceinline__ Tile decode_tile(int64_t unit, int ntm, int ntn) {
-  return {(int)(unit % ntm), (int)((unit / ntm) % ntn), (int)(unit / ((int64_t)ntm * ntn))};
-}
-
-__device__ __forceinline__ KRange slab_range(int slab, int64_t kslab, int64_t K) {
-  const int64_t k0 = (int64_t)slab * kslab;
-  return {k0, (k0 + kslab < K) ? k0 + kslab : K};
-}
-
-// epilogue: D[row = (lane>>4) + 4r][col = lane&15] per 16x16 accumulator; (ROW0, COL0) is the corner of the wave's NI x NJ
-// accumulators, entries past the M x N edge are dropped.  STORE is a statement that sees i, j, r, row and col.  A macro, not a
-// function template: through a functor the stores of the NT kernels compiled to another epilogue than the one measured.
-#define ISDF_STORE_ACC(NI, NJ, ROW0, COL0, M, N, STORE)                                       \
-  _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                            \
-    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                           \
-      const int row = ROW0 + i * 16 + (lane >> 4) + 4 * r;                                    \
-      if (row >= M) continue;                                                                 \
-      _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                        \
-        const int col = COL0 + j * 16 + (lane & 15);                                          \
-        if (col >= N) continue;                                                               \
-        STORE                                                                                 \
-      }                                                                                       \
-    }                                                                                         \
-  }
+// unit decode (xcd_unit / decode_tile / slab_range) and accumulator store (ISDF_STORE_ACC): gemm_tile.h, shared with thc.hip
 // STORE of the NT kernels: the slab's partial tile, or C itself (direct) with alpha and beta
 #define ISDF_SLAB_STORE                                                                       \
   {                                                                                           \

@@ -222,6 +222,9 @@ class Cell:
             if self._has_pseudo(std):
                 p = self.pseudo
                 pname = p.get(s, p.get(std)) if isinstance(p, dict) else p
+                if isinstance(pname, (list, tuple)):
+                    self._pseudo[s] = list(pname)       # the parameters themselves, in load_pseudo's layout (as PySCF's format_pseudo takes them)
+                    continue
                 try:
                     self._pseudo[s] = load_pseudo(pname, std)
                 except KeyError:

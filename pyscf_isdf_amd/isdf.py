@@ -1151,4 +1151,11 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
 
     get_mo_eri = ao2mo
 
+    # ---- correlated methods from the factorisation (thc_mp2.py) -------------
+    def mp2_os(self, mo_coeff, mo_energy, mo_occ, rtol=1e-8, c_os=1.3):
+        """Opposite-spin MP2 energy (SOS-MP2 with c_os) from the THC form of the factors on the device, cubic in the system size:
+        thc_mp2.mp2_os.  Closed shell, Gamma point, pair_space='ao'; everything else raises before any work."""
+        from .thc_mp2 import mp2_os
+        return mp2_os(self, mo_coeff, mo_energy, mo_occ, rtol=rtol, c_os=c_os)
+
 

@@ -133,6 +133,8 @@ SIGNATURES = {
     'isdf_gemm_nn_had': (c_int, [c_vp, c_int, c_i64, c_int, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_vp, c_i64]),
     'isdf_pack_table_pm': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_vp, c_i64]),
     'isdf_herm_kscale_nt': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_dbl, c_vp, c_vp, c_i64]),
+    'isdf_thc_pair': (c_int, [c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64]),
+    'isdf_trace_sq': (c_int, [c_vp, c_int, c_vp, c_i64, c_vp]),
     'isdf_get_k_exact': (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     'isdf_get_k': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp]),
 }
