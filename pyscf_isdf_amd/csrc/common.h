@@ -163,18 +163,23 @@ int gemm_nt_f64_scaled(isdf_handle h, int M, int N, int64_t K, double alpha, con
                        int64_t ldc);
 // Triangular solves by substitution (trsm.hip): L (m x m) lower triangular, row-major (reads the lower triangle only).
 //   left:  X (m x n, row-major) <- op(L)^-1 X      right: X (n x m, row-major) <- X op(L)^-1      op = L | L^T (trans)
+// left: the blocked walk of trsm.hip over 512-row panels whose diagonal solve is the walk over 64-row substitution blocks;
+// right: transpose, the left solve of the other op, transpose back
 int trsm_lower_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
 int trsm_lower_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
 // every diagonal block of a block-diagonal lower factor in one launch: X[blk_b, :] <- D_b^-1 X[blk_b, :] (blk_off on the host);
 // own_columns: block b solves its own columns [off_b, off_b + nb_b) only (isdf_block_invert: the others are zero and stay so)
 int block_forward_solve(isdf_handle h, const double* D, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
                         int64_t ldx, int64_t n, bool own_columns = false);
-// X[blk_b, :] <- Dinv_b X[blk_b, :] with explicit block inverses (lower triangular), MFMA kernel of trsm.hip
+// X[blk_b, :] <- Dinv_b X[blk_b, :] with explicit block inverses (lower triangular), MFMA kernels of trsm.hip: the
+// register-resident form for blocks of up to 256 rows, else the LDS form; square_input: the block apply squares X while staging it
 int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
                         int64_t ldx, int64_t n, bool square_input = false);
+// dst (cols x rows, ldd) = src (rows x cols, lds)^T
 int transpose_rm(isdf_handle h, const double* src, int64_t lds, int64_t rows, int64_t cols, double* dst, int64_t ldd);
-// The fit's triangular solves with a row-major lower factor L: dispatch on h->trsm_substitution between rocBLAS dtrsm
-// (column-major view: the same buffer is the upper factor U = L^T) and trsm_lower_*.
+// The fit's triangular solves with a row-major lower factor L: dispatch on h->trsm_substitution between trsm_lower_* and the
+// blocked walk of trsm.hip over blocks of 1024 rows with a rocBLAS dtrsm on each diagonal block (column-major view: the same
+// buffer is the upper factor U = L^T).
 int tri_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
 int tri_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx);
 // Row-major wrappers over rocBLAS for the well-shaped products.

@@ -74,10 +74,9 @@ extern "C" int isdf_fit_from_chol(isdf_handle h, double* d_L, int k, int64_t m, 
   ARG_CHECK(h, d_L && d_piv && k > 0 && m >= k && ldL >= m);
   double* T = (double*)isdf_ws(h, "fit_T", sizeof(double) * (size_t)k * k);
   if (!T) return ISDF_ERR_HIP;
-  dim3 grid((unsigned)cdiv(k, 256), (unsigned)k);
   ARG_CHECK(h, k <= 65535);
-  hipLaunchKernelGGL(gather_T_kernel, grid, dim3(256), 0, h->stream, d_L, ldL, d_piv, k, T);
-  KERNEL_CHECK(h);
+  int rc = isdf_gather_T(h, d_L, k, ldL, d_piv, T);      // its own checks hold after the ones above
+  if (rc) return rc;
   // Row-major Theta = T^-1 L  <=>  column-major X * (T as column-major = T^T, lower) = L^T.
   const double one = 1.0;
   ARG_CHECK(h, m < (int64_t)2147483647 && ldL < (int64_t)2147483647);
@@ -107,6 +106,90 @@ __global__ void max_diag_kernel(const double* __restrict__ A, int n, double* __r
 }
 }  // namespace
 
+// A (P, P) = (aoP aoP^T)^2, in complex mode (nh > 0, aoP stored [Re | Im]) (Re S)^2 + (Im S)^2 with Im S = aoP_rot aoP^T
+static int gram_sq(isdf_handle h, const double* d_aoP, int P, int nao, int nh, double* d_A) {
+  int rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, d_aoP, nao, d_aoP, nao, 0.0, d_A, P);
+  if (rc) return rc;
+  if (nh > 0) {
+    double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
+    double* tmp = (double*)isdf_ws(h, "fit_tmp", sizeof(double) * (size_t)P * P);
+    if (!rot || !tmp) return ISDF_ERR_HIP;
+    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
+    rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, rot, nao, d_aoP, nao, 0.0, tmp, P);
+    if (rc) return rc;
+    hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream, d_A,
+                       (int64_t)P, tmp, (int64_t)P, (int64_t)P);
+  } else {
+    hipLaunchKernelGGL(square_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream, d_A,
+                       (int64_t)P, (int64_t)P, (int64_t)P);
+  }
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+// B (P, ng) = (aoP ao)^2, in complex mode (aoP ao)^2 + (aoP_rot ao)^2 with the second product in chunks of 8192 columns
+static int pair_rows(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_ao, int64_t ng, int64_t ld,
+                     double* d_B, int64_t ldb) {
+  int rc = product_rows(h, P, ng, nao, d_aoP, d_ao, ld, d_B, ldb, nh == 0);
+  if (rc) return rc;
+  if (nh > 0) {
+    const int64_t CH = 8192;
+    double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
+    double* tmp = (double*)isdf_ws(h, "fit_tmpB", sizeof(double) * (size_t)P * CH);
+    if (!rot || !tmp) return ISDF_ERR_HIP;
+    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
+    for (int64_t c0 = 0; c0 < ng; c0 += CH) {
+      const int64_t nc = std::min(CH, ng - c0);
+      rc = gemm_rm(h, 'N', 'N', P, nc, nao, 1.0, rot, nao, d_ao + c0, ld, 0.0, tmp, CH);
+      if (rc) return rc;
+      hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(nc, 256), (unsigned)P), dim3(256), 0, h->stream,
+                         d_B + c0, ldb, tmp, CH, nc);
+    }
+  }
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+// A (P, P) <- A + rel * max(diag A) * I, the maximum through the device scalar maxdiag
+static int shift_diag(isdf_handle h, double* d_A, int P, double rel, double* maxdiag) {
+  hipLaunchKernelGGL(max_diag_kernel, dim3(1), dim3(256), 0, h->stream, d_A, P, maxdiag);
+  hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, h->stream, d_A, P, maxdiag, rel);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+// The shift ladder of the fit's factorisations: an over-complete point set makes the matrix numerically singular, and a
+// diagonal shift relative to its largest diagonal entry cures that.  attempt(i, reg), i = 0 .. attempts - 1, restores the
+// matrix, shifts it by reg where reg > 0 and factorises it (rocsolver_dpotrf with its status in the device word info);
+// the shifts are reg0, then 1e-14 if that was 0, then 100 times the last.  The first shift that factorises goes to *reg_used;
+// when none does, fail(the last shift tried, potrf's status: the failing minor) makes the caller's error.
+template <class Attempt, class Fail>
+static int shift_ladder(isdf_handle h, int attempts, double reg0, int* info, double* reg_used, Attempt attempt, Fail fail) {
+  double reg = reg0;
+  int h_info = 0;
+  for (int i = 0; i < attempts; ++i) {
+    const int rc = attempt(i, reg);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h_info == 0) {
+      if (reg_used) *reg_used = reg;
+      return ISDF_OK;
+    }
+    reg = (reg > 0.0) ? reg * 100.0 : 1e-14;
+  }
+  return fail(reg / 100.0, h_info);
+}
+
+// X (P, n) row-major <- L^-1 X (forward), L^-T X (backward) or both in that order (A^-1 X, A = L L^T); d_fac: the row-major
+// lower L == the column-major upper U of isdf_fit_prepare / isdf_chol_inplace.  Blocked left-looking (trsm.hip: tri_left)
+static int factor_solve(isdf_handle h, const double* d_fac, int P, double* d_X, int64_t n, int64_t ldx, bool forward,
+                        bool backward) {
+  const int rc = forward ? tri_left(h, false, P, n, d_fac, P, d_X, ldx) : ISDF_OK;
+  if (rc || !backward) return rc;
+  return tri_left(h, true, P, n, d_fac, P, d_X, ldx);
+}
+
 extern "C" int isdf_fit_prepare(isdf_handle h, const double* d_ao, int nao, int64_t ld,
                                 const int64_t* d_ip, int P, double reg_rel, double* d_aoP,
                                 double* d_chol, double* reg_used) {
@@ -120,51 +203,26 @@ extern "C" int isdf_fit_prepare_cplx(isdf_handle h, const double* d_ao, int nao,
   ARG_CHECK(h, nh == 0 || 2 * nh == nao);
   ARG_CHECK(h, d_ao && d_ip && d_aoP && d_chol && nao > 0 && P > 0 && reg_rel >= 0.0);
   ARG_CHECK(h, nao <= 65535 && P <= 65535);
-  hipLaunchKernelGGL(transpose_gather_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)nao), dim3(256), 0,
-                     h->stream, d_ao, ld, d_ip, P, nao, d_aoP);
-  KERNEL_CHECK(h);
+  int rc = isdf_gather_aoP(h, d_ao, nao, ld, d_ip, P, d_aoP);      // its own checks hold after the ones above
+  if (rc) return rc;
   int* info = (int*)isdf_ws(h, "fit_info", 256);
   if (!info) return ISDF_ERR_HIP;
   double* maxdiag = (double*)(info + 16);
-  double reg = reg_rel;
-  for (int attempt = 0; attempt < 5; ++attempt) {
-    // A_PP = (aoP aoP^T)^2 (+ reg * max diag * I), Cholesky A = U^T U in the column-major view
-    int rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, d_aoP, nao, d_aoP, nao, 0.0, d_chol, P);
-    if (rc) return rc;
-    if (nh > 0) {
-      // complex mode: A = (Re S)^2 + (Im S)^2, Im S = aoP_rot aoP^T
-      double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
-      double* tmp = (double*)isdf_ws(h, "fit_tmp", sizeof(double) * (size_t)P * P);
-      if (!rot || !tmp) return ISDF_ERR_HIP;
-      hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
-      rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, rot, nao, d_aoP, nao, 0.0, tmp, P);
-      if (rc) return rc;
-      hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream,
-                         d_chol, (int64_t)P, tmp, (int64_t)P, (int64_t)P);
-    } else {
-      hipLaunchKernelGGL(square_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream,
-                         d_chol, (int64_t)P, (int64_t)P, (int64_t)P);
-    }
-    if (reg > 0.0) {
-      hipLaunchKernelGGL(max_diag_kernel, dim3(1), dim3(256), 0, h->stream, d_chol, P, maxdiag);
-      hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, h->stream, d_chol, P,
-                         maxdiag, reg);
-    }
-    KERNEL_CHECK(h);
-    { ProfScope ps(h, "rocsolver_dpotrf[flop]", (double)P * P * P / 3.0);
-    BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, P, d_chol, P, info)); }
-    int h_info = 0;
-    HIP_TRY(h, hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h_info == 0) {
-      if (reg_used) *reg_used = reg;
-      return ISDF_OK;
-    }
-    reg = (reg > 0.0) ? reg * 100.0 : 1e-14;
-  }
-  return isdf_fail(h, ISDF_ERR_NUM,
-                   "A_PP = (aoP aoP^T)^2 is not numerically positive definite even with diagonal shift %g * max diag",
-                   reg / 100.0);
+  return shift_ladder(
+      h, 5, reg_rel, info, reg_used,
+      [&](int, double reg) {
+        // A_PP = (aoP aoP^T)^2 (+ reg * max diag * I), rebuilt at every attempt; Cholesky A = U^T U in the column-major view
+        int rc = gram_sq(h, d_aoP, P, nao, nh, d_chol);
+        if (!rc && reg > 0.0) rc = shift_diag(h, d_chol, P, reg, maxdiag);
+        if (rc) return rc;
+        ProfScope ps(h, "rocsolver_dpotrf[flop]", (double)P * P * P / 3.0);
+        BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, P, d_chol, P, info));
+        return ISDF_OK;
+      },
+      [&](double reg, int) {
+        return isdf_fail(h, ISDF_ERR_NUM,
+                         "A_PP = (aoP aoP^T)^2 is not numerically positive definite even with diagonal shift %g * max diag", reg);
+      });
 }
 
 extern "C" int isdf_fit_apply(isdf_handle h, const double* d_chol, const double* d_aoP, int P, int nao,
@@ -182,29 +240,11 @@ extern "C" int isdf_fit_apply_cplx(isdf_handle h, const double* d_chol, const do
   ARG_CHECK(h, P <= 65535 && ldt < (int64_t)2147483647 && ng < (int64_t)2147483647);
   // B = (aoP ao)^2 (P x ng, row-major) written straight into theta; then in the column-major view
   // X = B_cm U^-1 U^-T  (A = U^T U).
-  int rc = product_rows(h, P, ng, nao, d_aoP, d_ao, ld, d_theta, ldt, nh == 0);
+  int rc = pair_rows(h, d_aoP, P, nao, nh, d_ao, ng, ld, d_theta, ldt);
   if (rc) return rc;
-  if (nh > 0) {
-    // complex mode: B = (aoP X)^2 + (aoP_rot X)^2, the second product in column chunks
-    const int64_t CH = 8192;
-    double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
-    double* tmp = (double*)isdf_ws(h, "fit_tmpB", sizeof(double) * (size_t)P * CH);
-    if (!rot || !tmp) return ISDF_ERR_HIP;
-    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
-    for (int64_t c0 = 0; c0 < ng; c0 += CH) {
-      const int64_t nc = std::min(CH, ng - c0);
-      rc = gemm_rm(h, 'N', 'N', P, nc, nao, 1.0, rot, nao, d_ao + c0, ld, 0.0, tmp, CH);
-      if (rc) return rc;
-      hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(nc, 256), (unsigned)P), dim3(256), 0, h->stream,
-                         d_theta + c0, ldt, tmp, CH, nc);
-    }
-  }
-  KERNEL_CHECK(h);
   // Theta = A^-1 B with A = Lr Lr^T (Lr = the factor read row-major, lower): forward solve Y = Lr^-1 B, then (unless the
-  // caller wants Y, see isdf_W_from_factor) the backward solve Theta = Lr^-T Y; blocked left-looking (trsm.hip: tri_left)
-  rc = tri_left(h, false, P, ng, d_chol, P, d_theta, ldt);
-  if (rc || forward_only) return rc;
-  return tri_left(h, true, P, ng, d_chol, P, d_theta, ldt);
+  // caller wants Y, see isdf_W_from_factor) the backward solve Theta = Lr^-T Y
+  return factor_solve(h, d_chol, P, d_theta, ng, ldt, true, !forward_only);
 }
 
 extern "C" int isdf_fit_global(isdf_handle h, const double* d_ao, int nao, int64_t ngrids, int64_t ld,
@@ -268,23 +308,7 @@ extern "C" int isdf_W_from_factor(isdf_handle h, const double* d_F, int P, int k
 extern "C" int isdf_gram_sq(isdf_handle h, const double* d_aoP, int P, int nao, int nh, double* d_A) {
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_aoP && d_A && P > 0 && nao > 0 && P <= 65535 && (nh == 0 || 2 * nh == nao));
-  int rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, d_aoP, nao, d_aoP, nao, 0.0, d_A, P);
-  if (rc) return rc;
-  if (nh > 0) {
-    double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
-    double* tmp = (double*)isdf_ws(h, "fit_tmp", sizeof(double) * (size_t)P * P);
-    if (!rot || !tmp) return ISDF_ERR_HIP;
-    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
-    rc = gemm_rm(h, 'N', 'T', P, P, nao, 1.0, rot, nao, d_aoP, nao, 0.0, tmp, P);
-    if (rc) return rc;
-    hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream, d_A,
-                       (int64_t)P, tmp, (int64_t)P, (int64_t)P);
-  } else {
-    hipLaunchKernelGGL(square_kernel, dim3((unsigned)cdiv(P, 256), (unsigned)P), dim3(256), 0, h->stream, d_A,
-                       (int64_t)P, (int64_t)P, (int64_t)P);
-  }
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return gram_sq(h, d_aoP, P, nao, nh, d_A);
 }
 
 extern "C" int isdf_pair_gram_rows(isdf_handle h, const double* d_aoP, int P, int nao, int nh, const double* d_ao,
@@ -292,24 +316,7 @@ extern "C" int isdf_pair_gram_rows(isdf_handle h, const double* d_aoP, int P, in
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_aoP && d_ao && d_B && P > 0 && P <= 65535 && nao > 0 && ng > 0 && ld >= ng && ldb >= ng);
   ARG_CHECK(h, nh == 0 || 2 * nh == nao);
-  int rc = product_rows(h, P, ng, nao, d_aoP, d_ao, ld, d_B, ldb, nh == 0);
-  if (rc) return rc;
-  if (nh > 0) {
-    const int64_t CH = 8192;
-    double* rot = (double*)isdf_ws(h, "fit_rot", sizeof(double) * (size_t)P * nao);
-    double* tmp = (double*)isdf_ws(h, "fit_tmpB", sizeof(double) * (size_t)P * CH);
-    if (!rot || !tmp) return ISDF_ERR_HIP;
-    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)cdiv(nao, 256), (unsigned)P), dim3(256), 0, h->stream, d_aoP, P, nh, rot);
-    for (int64_t c0 = 0; c0 < ng; c0 += CH) {
-      const int64_t nc = std::min(CH, ng - c0);
-      rc = gemm_rm(h, 'N', 'N', P, nc, nao, 1.0, rot, nao, d_ao + c0, ld, 0.0, tmp, CH);
-      if (rc) return rc;
-      hipLaunchKernelGGL(square_add_kernel, dim3((unsigned)cdiv(nc, 256), (unsigned)P), dim3(256), 0, h->stream,
-                         d_B + c0, ldb, tmp, CH, nc);
-    }
-  }
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return pair_rows(h, d_aoP, P, nao, nh, d_ao, ng, ld, d_B, ldb);
 }
 
 namespace {
@@ -378,25 +385,28 @@ extern "C" int isdf_block_chol(isdf_handle h, const double* d_A, int P, int nblk
     // D is only a preconditioner: any invertible block works as long as the same D is used throughout, so a block
     // that is not numerically positive definite (its points were selected on slightly different AO values, or the
     // set is over-complete) simply gets a larger diagonal shift: shift_rel, then 1e-14, x100 per retry
-    double reg = shift_rel;
-    int h_info = 1;
-    for (int attempt = 0; attempt < 6 && h_info != 0; ++attempt) {
-      hipLaunchKernelGGL(copy_block_kernel, dim3((unsigned)cdiv(nb, 128), (unsigned)nb), dim3(128), 0, h->stream, d_A, P,
-                         off, nb, d_D);
-      if (reg > 0)
-        hipLaunchKernelGGL(add_diag_const_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, h->stream,
-                           d_D + (int64_t)off * P + off, nb, (int64_t)P, reg * md);
-      KERNEL_CHECK(h);
-      // column-major upper factor of the block == row-major lower D_b (A_bb = D_b D_b^T)
-      BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, nb, d_D + (int64_t)off * P + off, P, info));
-      HIP_TRY(h, hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      if (h_info == 0) { worst = std::max(worst, reg); break; }
-      reg = (reg > 0.0) ? reg * 100.0 : 1e-14;
-    }
-    if (h_info != 0)
-      return isdf_fail(h, ISDF_ERR_NUM, "diagonal block %d of A_PP is not positive definite even with shift %g * max diag "
-                       "(minor %d of %d)", b, reg / 100.0, h_info, nb);
+    // The block is copied afresh at every attempt and shifted by the host value reg * (max diag of the whole A)
+    double* Db = d_D + (int64_t)off * P + off;
+    double used = 0.0;
+    const int rc = shift_ladder(
+        h, 6, shift_rel, info, &used,
+        [&](int, double reg) {
+          hipLaunchKernelGGL(copy_block_kernel, dim3((unsigned)cdiv(nb, 128), (unsigned)nb), dim3(128), 0, h->stream, d_A, P,
+                             off, nb, d_D);
+          if (reg > 0)
+            hipLaunchKernelGGL(add_diag_const_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, h->stream, Db, nb,
+                               (int64_t)P, reg * md);
+          KERNEL_CHECK(h);
+          // column-major upper factor of the block == row-major lower D_b (A_bb = D_b D_b^T)
+          BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, nb, Db, P, info));
+          return ISDF_OK;
+        },
+        [&](double reg, int minor) {
+          return isdf_fail(h, ISDF_ERR_NUM, "diagonal block %d of A_PP is not positive definite even with shift %g * max diag "
+                           "(minor %d of %d)", b, reg, minor, nb);
+        });
+    if (rc) return rc;
+    worst = std::max(worst, used);
   }
   if (shift_used) *shift_used = worst;
   return ISDF_OK;
@@ -507,11 +517,7 @@ extern "C" int isdf_shift_diag(isdf_handle h, double* d_A, int P, double shift_r
   if (shift_rel == 0.0) return ISDF_OK;
   int* info = (int*)isdf_ws(h, "fit_info", 256);
   if (!info) return ISDF_ERR_HIP;
-  double* maxdiag = (double*)(info + 16);
-  hipLaunchKernelGGL(max_diag_kernel, dim3(1), dim3(256), 0, h->stream, d_A, P, maxdiag);
-  hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, h->stream, d_A, P, maxdiag, shift_rel);
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  return shift_diag(h, d_A, P, shift_rel, (double*)(info + 16));
 }
 
 extern "C" int isdf_chol_inplace(isdf_handle h, double* d_A, int P, double shift_rel, double* d_scratch,
@@ -524,29 +530,23 @@ extern "C" int isdf_chol_inplace(isdf_handle h, double* d_A, int P, double shift
   if (!info || !keep) return ISDF_ERR_HIP;
   double* maxdiag = (double*)(info + 16);
   HIP_TRY(h, hipMemcpyAsync(keep, d_A, sizeof(double) * (size_t)P * P, hipMemcpyDeviceToDevice, h->stream));
-  // same ladder as isdf_fit_prepare: an over-complete point set makes the matrix numerically singular
-  double reg = shift_rel;
-  for (int attempt = 0; attempt < 5; ++attempt) {
-    if (attempt > 0)
-      HIP_TRY(h, hipMemcpyAsync(d_A, keep, sizeof(double) * (size_t)P * P, hipMemcpyDeviceToDevice, h->stream));
-    if (reg > 0) {
-      hipLaunchKernelGGL(max_diag_kernel, dim3(1), dim3(256), 0, h->stream, d_A, P, maxdiag);
-      hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, h->stream, d_A, P, maxdiag, reg);
-      KERNEL_CHECK(h);
-    }
-    { ProfScope ps(h, "rocsolver_dpotrf[flop]", (double)P * P * P / 3.0);
-      BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, P, d_A, P, info)); }
-    int h_info = 0;
-    HIP_TRY(h, hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h_info == 0) {
-      if (reg_used) *reg_used = reg;
-      return ISDF_OK;
-    }
-    reg = (reg > 0.0) ? reg * 100.0 : 1e-14;
-  }
-  return isdf_fail(h, ISDF_ERR_NUM, "matrix is not numerically positive definite even with diagonal shift %g * max diag",
-                   reg / 100.0);
+  return shift_ladder(
+      h, 5, shift_rel, info, reg_used,
+      [&](int attempt, double reg) {
+        if (attempt > 0)
+          HIP_TRY(h, hipMemcpyAsync(d_A, keep, sizeof(double) * (size_t)P * P, hipMemcpyDeviceToDevice, h->stream));
+        if (reg > 0) {
+          const int rc = shift_diag(h, d_A, P, reg, maxdiag);
+          if (rc) return rc;
+        }
+        ProfScope ps(h, "rocsolver_dpotrf[flop]", (double)P * P * P / 3.0);
+        BLAS_TRY(h, rocsolver_dpotrf(h->blas, rocblas_fill_upper, P, d_A, P, info));
+        return ISDF_OK;
+      },
+      [&](double reg, int) {
+        return isdf_fail(h, ISDF_ERR_NUM, "matrix is not numerically positive definite even with diagonal shift %g * max diag",
+                         reg);
+      });
 }
 
 extern "C" int isdf_factor_solve(isdf_handle h, const double* d_fac, int P, double* d_X, int64_t n, int64_t ldx) {
@@ -554,9 +554,7 @@ extern "C" int isdf_factor_solve(isdf_handle h, const double* d_fac, int P, doub
   // isdf_fit_prepare / isdf_chol_inplace)
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_fac && d_X && P > 0 && n > 0 && ldx >= n && n < 2147483647LL && ldx < 2147483647LL);
-  int rc = tri_left(h, false, P, n, d_fac, P, d_X, ldx);
-  if (rc) return rc;
-  return tri_left(h, true, P, n, d_fac, P, d_X, ldx);
+  return factor_solve(h, d_fac, P, d_X, n, ldx, true, true);
 }
 
 extern "C" int isdf_bj_probe_vectors(isdf_handle h, double* d_T, int n, const double* d_fac, const double* d_D, int P,
@@ -787,7 +785,7 @@ extern "C" int isdf_factor_solve_half(isdf_handle h, const double* d_fac, int P,
   // of the Cholesky fit route for rows the caller produced itself (isdf_pair_prod_rows)
   if (!h) return ISDF_ERR_ARG;
   ARG_CHECK(h, d_fac && d_X && P > 0 && n > 0 && ldx >= n && n < 2147483647LL && ldx < 2147483647LL);
-  return tri_left(h, backward != 0, P, n, d_fac, P, d_X, ldx);
+  return factor_solve(h, d_fac, P, d_X, n, ldx, backward == 0, backward != 0);
 }
 
 extern "C" int isdf_gather_aoP(isdf_handle h, const double* d_ao, int nao, int64_t ld, const int64_t* d_ip, int P,

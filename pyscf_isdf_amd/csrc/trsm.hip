@@ -9,12 +9,14 @@
 // read through the scalar cache, and everything off the diagonal is rocBLAS dgemm; right-sided solves are left-sided ones
 // on the transpose.  Measured: the two give the same K to the noise level of the block-Jacobi route on every case tried
 // (He2 test cell, diamond 2x2x2 / 4x4x4), rocBLAS is faster (12.4 s against 12.8 s per step at 4x4x4; many small launches
-// here), so rocBLAS stays the default; this path is a cross-check that does not share rocBLAS's algorithm.  (Round 1 ran its
-// rocprofv3 --pmc passes through it after a profiler crash attributed to rocBLAS's trsm on 1.7M-column right-hand sides; the
-// isolated call with those arguments profiles cleanly - profiles/r02_trsm_under_pmc_repro.log - and the default fit route
-// never calls dtrsm over the grid, so PMC passes of the default command need no switch.)
+// here), so rocBLAS stays the default; this path is a cross-check that does not share rocBLAS's algorithm.
+//
+// Both paths are one host body, blocked_walk below: the default is the walk over blocks of 1024 rows with a rocBLAS dtrsm
+// on each diagonal block, the substitution path the walk over panels of 512 rows whose diagonal solve is the walk over 64
+// rows with subst_kernel.  The file also holds the block-diagonal kernels of the block-Jacobi route: block_forward_kernel
+// (all block factors in one launch) and the two block-apply kernels (explicit block inverses on the matrix cores).
 #include "common.h"
-#include <cstdlib>
+#include <algorithm>
 
 namespace {
 
@@ -314,36 +316,46 @@ __global__ __launch_bounds__(64 * ((NT + 1) / 2)) __attribute__((amdgpu_waves_pe
   }
 }
 
-template <int NT, int NCT>
-static int block_apply_reg_launch(isdf_handle h, const double* Dinv, int64_t ldd, int nblk, const int32_t* d_off, double* X,
-                                  int64_t ldx, int64_t n, bool sq) {
-  constexpr int TN = 16 * NCT;
-  constexpr int NTHREADS = 64 * ((NT + 1) / 2);
-  static_assert(NTHREADS % TN == 0 && (16 * NT * TN) % NTHREADS == 0, "tile elements must divide evenly over the threads");
-  const size_t lds = (size_t)16 * NT * (TN + 2) * sizeof(double);
-  const int64_t ntile = (n + TN - 1) / TN;
-  // workgroups per block: `block_apply_waves` (default 16) times the CU count in all - 2.24 TB/s with 4, 2.6-2.7 with 16-32 at
-  // 1.7 M columns (tools/bench_block_apply.py): short serial chains per workgroup matter more than re-reading the block inverse
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntile, ((int64_t)h->num_cu * h->block_apply_waves + nblk - 1) / nblk));
-  if (sq) {
-    if (lds > 64 * 1024)
-      HIP_TRY(h, hipFuncSetAttribute((const void*)&block_apply_reg_kernel<NT, NCT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(block_apply_reg_kernel<NT, NCT, true>), dim3(gx, (unsigned)nblk), dim3(NTHREADS), lds, h->stream,
-                       Dinv, ldd, d_off, X, ldx, n);
-  } else {
-    if (lds > 64 * 1024)
-      HIP_TRY(h, hipFuncSetAttribute((const void*)&block_apply_reg_kernel<NT, NCT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(block_apply_reg_kernel<NT, NCT, false>), dim3(gx, (unsigned)nblk), dim3(NTHREADS), lds, h->stream,
-                       Dinv, ldd, d_off, X, ldx, n);
-  }
+// ---- block apply: one launcher, one table per form ------------------------------------------------------
+using BlockApplyKernel = void (*)(const double*, int64_t, const int32_t*, double*, int64_t, int64_t);
+
+// one block-apply launch; a request of more than 64 KB of dynamic LDS needs the kernel's attribute raised, which is done
+// at every such launch (the call is cheap next to the launch and needs no per-device bookkeeping)
+static int block_apply_launch(isdf_handle h, BlockApplyKernel kernel, dim3 grid, int threads, size_t lds, const double* Dinv,
+                              int64_t ldd, const int32_t* d_off, double* X, int64_t ldx, int64_t n) {
+  if (lds > 64 * 1024)
+    HIP_TRY(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, h->stream, Dinv, ldd, d_off, X, ldx, n);
   KERNEL_CHECK(h);
   return ISDF_OK;
 }
 
-template <int TN, bool SQ>
-static hipError_t block_apply_lds_attr() {
-  return hipFuncSetAttribute((const void*)&block_apply_mfma_kernel<TN, SQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// An instantiation of either form: taken by the first row whose limit holds, under the name rocprofv3 gives it (SQ left out).
+struct BlockApplyRow {
+  size_t limit;                  // register form: row tiles of 16 it holds; LDS form: bytes of LDS the block's rows may take
+  const char* label;
+  BlockApplyKernel kernel[2];    // [SQ]
+  int tn;                        // columns per tile
+  int threads;
+};
+template <int NT, int NCT>
+static constexpr BlockApplyRow reg_row(const char* label) {
+  constexpr int TN = 16 * NCT, NTHREADS = 64 * ((NT + 1) / 2);
+  static_assert(NTHREADS % TN == 0 && (16 * NT * TN) % NTHREADS == 0, "tile elements must divide evenly over the threads");
+  return {NT, label, {block_apply_reg_kernel<NT, NCT, false>, block_apply_reg_kernel<NT, NCT, true>}, TN, NTHREADS};
 }
+template <int TN>
+static constexpr BlockApplyRow lds_row(size_t kb, const char* label) {
+  return {kb * 1024, label, {block_apply_mfma_kernel<TN, false>, block_apply_mfma_kernel<TN, true>}, TN, 256};
+}
+// register-resident form, blocks of up to 256 rows: <16,1> takes every block the others do not
+static const BlockApplyRow REG_ROWS[] = {
+    reg_row<8, 2>("block_apply_reg_kernel<8,2>[byte]"), reg_row<10, 2>("block_apply_reg_kernel<10,2>[byte]"),
+    reg_row<12, 2>("block_apply_reg_kernel<12,2>[byte]"), reg_row<16, 1>("block_apply_reg_kernel<16,1>[byte]")};
+// LDS form: 64 columns per workgroup while the block's rows fit 52 KB of LDS (three workgroups per CU), else 32, else 16
+static const BlockApplyRow LDS_ROWS[] = {lds_row<64>(52, "block_apply_mfma_kernel<64>[byte]"),
+                                         lds_row<32>(80, "block_apply_mfma_kernel<32>[byte]"),
+                                         lds_row<16>(160, "block_apply_mfma_kernel<16>[byte]")};
 
 int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
                         int64_t ldx, int64_t n, bool square_input) {
@@ -352,53 +364,30 @@ int block_apply_inverse(isdf_handle h, const double* Dinv, int64_t ldd, int nblk
   for (int b = 0; b < nblk; ++b) mmax = std::max(mmax, blk_off_host[b + 1] - blk_off_host[b]);
   const int mpad = (mmax + 31) & ~31;
   ARG_CHECK(h, mmax > 0);
-  // which instantiation runs, under the name rocprofv3 gives it (SQ left out).  Register-resident form for blocks of up to 256
-  // rows (option "block_apply_reg", default on); else 64 columns per workgroup while the block's rows fit 52 KB of LDS (three
-  // workgroups per CU), else 32, else 16
+  // register-resident form for blocks of up to 256 rows (option "block_apply_reg", default on), else the LDS form
   const bool reg = h->block_apply_reg && mmax <= 256;
-  const int nt = (mmax + 15) / 16;
-  int tn = 0;
-  const char* label;
-  if (reg) {
-    label = nt <= 8 ? "block_apply_reg_kernel<8,2>[byte]" : nt <= 10 ? "block_apply_reg_kernel<10,2>[byte]"
-          : nt <= 12 ? "block_apply_reg_kernel<12,2>[byte]" : "block_apply_reg_kernel<16,1>[byte]";
-  } else if ((size_t)mpad * (64 + 2) * sizeof(double) <= 52 * 1024) {
-    tn = 64; label = "block_apply_mfma_kernel<64>[byte]";
-  } else if ((size_t)mpad * (32 + 2) * sizeof(double) <= 80 * 1024) {
-    tn = 32; label = "block_apply_mfma_kernel<32>[byte]";
-  } else {
-    ARG_CHECK(h, (size_t)mpad * (16 + 2) * sizeof(double) <= 160 * 1024);
-    tn = 16; label = "block_apply_mfma_kernel<16>[byte]";
-  }
+  // what a row's limit bounds: the block's row tiles of 16, or the LDS its padded rows take at the row's tile width
+  auto need = [&](const BlockApplyRow& r) {
+    return reg ? (size_t)(mmax + 15) / 16 : (size_t)mpad * (r.tn + 2) * sizeof(double);
+  };
+  const BlockApplyRow* row = reg ? REG_ROWS : LDS_ROWS;
+  const BlockApplyRow* const last = row + (reg ? 3 : 2);
+  while (row != last && need(*row) > row->limit) ++row;
+  ARG_CHECK(h, need(*row) <= row->limit || reg);        // LDS form: the rows must fit 160 KB even 16 columns wide
+  // dynamic LDS: the padded rows of a tile (the register form pads to the 16 NT rows of its instantiation)
+  const size_t lds = (size_t)(reg ? 16 * (int)row->limit : mpad) * (row->tn + 2) * sizeof(double);
   int32_t* d_off = (int32_t*)isdf_ws(h, "trsm_blk_off", sizeof(int32_t) * (size_t)(nblk + 1));
   if (!d_off) return ISDF_ERR_HIP;
   HIP_TRY(h, hipMemcpyAsync(d_off, blk_off_host, sizeof(int32_t) * (size_t)(nblk + 1), hipMemcpyHostToDevice, h->stream));
-  ProfScope ps(h, label, 16.0 * (double)blk_off_host[nblk] * (double)n);
-  if (reg) {
-    if (nt <= 8) return block_apply_reg_launch<8, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
-    if (nt <= 10) return block_apply_reg_launch<10, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
-    if (nt <= 12) return block_apply_reg_launch<12, 2>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
-    return block_apply_reg_launch<16, 1>(h, Dinv, ldd, nblk, d_off, X, ldx, n, square_input);
-  }
-  // more than 64 KB of dynamic LDS needs the attribute raised once per instantiation (per device: kept in the handle's option map)
-#define ISDF_BA_LAUNCH(TN_, SQ_)                                                                                       \
-  do {                                                                                                                 \
-    if ((size_t)mpad * (TN_ + 2) * sizeof(double) > 64 * 1024) {                                                       \
-      HIP_TRY(h, (block_apply_lds_attr<TN_, SQ_>()));                                                                  \
-    }                                                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(block_apply_mfma_kernel<TN_, SQ_>), dim3((unsigned)cdiv(n, TN_), (unsigned)nblk),   \
-                       dim3(256), (size_t)mpad * (TN_ + 2) * sizeof(double), h->stream, Dinv, ldd, d_off, X, ldx, n);  \
-  } while (0)
-  if (tn == 64) {
-    if (square_input) ISDF_BA_LAUNCH(64, true); else ISDF_BA_LAUNCH(64, false);
-  } else if (tn == 32) {
-    if (square_input) ISDF_BA_LAUNCH(32, true); else ISDF_BA_LAUNCH(32, false);
-  } else {
-    if (square_input) ISDF_BA_LAUNCH(16, true); else ISDF_BA_LAUNCH(16, false);
-  }
-#undef ISDF_BA_LAUNCH
-  KERNEL_CHECK(h);
-  return ISDF_OK;
+  ProfScope ps(h, row->label, 16.0 * (double)blk_off_host[nblk] * (double)n);
+  const int64_t ntile = cdiv(n, row->tn);
+  // register form, workgroups per block: `block_apply_waves` (default 16) times the CU count in all - 2.24 TB/s with 4, 2.6-2.7
+  // with 16-32 at 1.7 M columns (tools/bench_block_apply.py): short serial chains per workgroup matter more than re-reading the
+  // block inverse.  LDS form: one workgroup per column tile
+  const int64_t gx = reg ? std::max<int64_t>(1, std::min<int64_t>(ntile, ((int64_t)h->num_cu * h->block_apply_waves + nblk - 1) / nblk))
+                         : ntile;
+  return block_apply_launch(h, row->kernel[square_input ? 1 : 0], dim3((unsigned)gx, (unsigned)nblk), row->threads, lds,
+                            Dinv, ldd, d_off, X, ldx, n);
 }
 
 int block_forward_solve(isdf_handle h, const double* D, int64_t ldd, int nblk, const int32_t* blk_off_host, double* X,
@@ -430,54 +419,42 @@ int transpose_rm(isdf_handle h, const double* src, int64_t lds, int64_t rows, in
   return ISDF_OK;
 }
 
-int trsm_lower_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
-  ARG_CHECK(h, L && X && m > 0 && n > 0 && ldl >= m && ldx >= n);
-  // two levels: panels of PB rows are updated with one large dgemm each, the panel's own triangle goes through
-  // 64-row substitution blocks with small dgemm updates inside the panel
-  const int PB = 512;
-  int rc;
-  if (!trans) {
-    for (int r0 = 0; r0 < m; r0 += PB) {
-      const int r1 = std::min(m, r0 + PB);
-      if (r0 > 0) {   // X[r0:r1] -= L[r0:r1, 0:r0] X[0:r0]
-        rc = gemm_rm(h, 'N', 'N', r1 - r0, n, r0, -1.0, L + (int64_t)r0 * ldl, ldl, X, ldx, 1.0, X + (int64_t)r0 * ldx, ldx);
-        if (rc) return rc;
-      }
-      for (int s0 = r0; s0 < r1; s0 += SB) {
-        const int s1 = std::min(r1, s0 + SB);
-        if (s0 > r0) {   // X[s0:s1] -= L[s0:s1, r0:s0] X[r0:s0]
-          rc = gemm_rm(h, 'N', 'N', s1 - s0, n, s0 - r0, -1.0, L + (int64_t)s0 * ldl + r0, ldl, X + (int64_t)r0 * ldx, ldx,
-                       1.0, X + (int64_t)s0 * ldx, ldx);
-          if (rc) return rc;
-        }
-        rc = subst(h, false, L + (int64_t)s0 * ldl + s0, ldl, s1 - s0, X + (int64_t)s0 * ldx, ldx, n);
-        if (rc) return rc;
-      }
+// ---- the blocked walk ------------------------------------------------------------------------------------
+// X <- op(L)^-1 X (X m x n) or, `right`, X <- X op(L)^-1 (X n x m), op = L | L^T (trans), block by block and LEFT-looking:
+// block [j0, j1) of X's rows (right: columns) first receives the contribution of all finished blocks in ONE deep dgemm (the
+// shape rocBLAS runs at the MFMA rate, and it only reads finished rows), then diag(j1 - j0, the diagonal block of L, the
+// block of X) solves it.  Blocks of nb from row 0; L^-1 X and X L^-T walk them upwards (finished: [0, j0), coupled through
+// L[j0:j1, 0:j0]), L^-T X and X L^-1 downwards (finished: [j1, m), coupled through L[j1:m, j0:j1]).
+template <class Diag>
+static int blocked_walk(isdf_handle h, bool right, bool trans, int nb, int m, int64_t n, const double* L, int64_t ldl, double* X,
+                        int64_t ldx, Diag diag) {
+  const bool up = right == trans;
+  const int64_t xs = right ? 1 : ldx;                      // stride of X along the triangular dimension
+  const int nblk = (int)cdiv(m, nb);
+  for (int i = 0; i < nblk; ++i) {
+    const int j0 = (up ? i : nblk - 1 - i) * nb, j1 = std::min(m, j0 + nb);
+    const int f0 = up ? 0 : j1, k = up ? j0 : m - j1;      // the finished rows [f0, f0 + k)
+    if (k > 0) {
+      const double* Lc = up ? L + (int64_t)j0 * ldl : L + (int64_t)j1 * ldl + j0;
+      const int rc = right ? gemm_rm(h, 'N', trans ? 'T' : 'N', n, j1 - j0, k, -1.0, X + f0 * xs, ldx, Lc, ldl, 1.0, X + j0 * xs, ldx)
+                           : gemm_rm(h, trans ? 'T' : 'N', 'N', j1 - j0, n, k, -1.0, Lc, ldl, X + f0 * xs, ldx, 1.0, X + j0 * xs, ldx);
+      if (rc) return rc;
     }
-  } else {
-    // L^T x = b: from the bottom up; the coupling of rows [a, b) to later rows [b, e) is L[b:e, a:b]^T
-    const int npan = (int)cdiv(m, PB);
-    for (int p = npan - 1; p >= 0; --p) {
-      const int r0 = p * PB, r1 = std::min(m, r0 + PB);
-      if (r1 < m) {   // X[r0:r1] -= L[r1:m, r0:r1]^T X[r1:m]
-        rc = gemm_rm(h, 'T', 'N', r1 - r0, n, m - r1, -1.0, L + (int64_t)r1 * ldl + r0, ldl, X + (int64_t)r1 * ldx, ldx, 1.0,
-                     X + (int64_t)r0 * ldx, ldx);
-        if (rc) return rc;
-      }
-      const int nsb = (int)cdiv(r1 - r0, SB);
-      for (int q = nsb - 1; q >= 0; --q) {
-        const int s0 = r0 + q * SB, s1 = std::min(r1, s0 + SB);
-        if (s1 < r1) {   // X[s0:s1] -= L[s1:r1, s0:s1]^T X[s1:r1]
-          rc = gemm_rm(h, 'T', 'N', s1 - s0, n, r1 - s1, -1.0, L + (int64_t)s1 * ldl + s0, ldl, X + (int64_t)s1 * ldx, ldx,
-                       1.0, X + (int64_t)s0 * ldx, ldx);
-          if (rc) return rc;
-        }
-        rc = subst(h, true, L + (int64_t)s0 * ldl + s0, ldl, s1 - s0, X + (int64_t)s0 * ldx, ldx, n);
-        if (rc) return rc;
-      }
-    }
+    const int rc = diag(j1 - j0, L + (int64_t)j0 * ldl + j0, X + j0 * xs);
+    if (rc) return rc;
   }
   return ISDF_OK;
+}
+
+int trsm_lower_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
+  ARG_CHECK(h, L && X && m > 0 && n > 0 && ldl >= m && ldx >= n);
+  // two levels: panels of 512 rows are updated with one large dgemm each, the panel's own triangle goes through
+  // 64-row substitution blocks with small dgemm updates inside the panel
+  return blocked_walk(h, false, trans, 512, m, n, L, ldl, X, ldx, [&](int pm, const double* Lp, double* Xp) {
+    return blocked_walk(h, false, trans, SB, pm, n, Lp, ldl, Xp, ldx, [&](int bm, const double* Lb, double* Xb) {
+      return subst(h, trans, Lb, ldl, bm, Xb, ldx, n);
+    });
+  });
 }
 
 int trsm_lower_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
@@ -497,94 +474,34 @@ int trsm_lower_right(isdf_handle h, bool trans, int m, int64_t n, const double* 
 //   L^-1 X   <->  X^T U^-1      L^-T X  <->  X^T U^-T      (rocBLAS side right)
 //   X L^-1   <->  U^-1 X^T      X L^-T  <->  U^-T X^T      (rocBLAS side left)
 namespace {
-int trsm_block_size() {
-  static const int nb = getenv("ISDF_TRSM_NB") ? std::max(64, atoi(getenv("ISDF_TRSM_NB"))) : 1024;
-  return nb;
-}
-// one rocBLAS dtrsm, column-major view (see the table above)
-int rb_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
+constexpr int TRSM_NB = 1024;      // rows per block of the default walk
+// one rocBLAS dtrsm with the m x m factor, column-major view (see the table above): side right takes X^T (n x m), left (m x n)
+int rb_trsm(isdf_handle h, rocblas_side side, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
   const double one = 1.0;
+  const bool r = side == rocblas_side_right;
   ProfScope ps(h, "rocblas_dtrsm[flop]", (double)n * m * m);
-  BLAS_TRY(h, rocblas_dtrsm(h->blas, rocblas_side_right, rocblas_fill_upper,
-                            trans ? rocblas_operation_transpose : rocblas_operation_none, rocblas_diagonal_non_unit,
-                            (rocblas_int)n, m, &one, L, (rocblas_int)ldl, X, (rocblas_int)ldx));
-  return ISDF_OK;
-}
-int rb_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
-  const double one = 1.0;
-  ProfScope ps(h, "rocblas_dtrsm[flop]", (double)n * m * m);
-  BLAS_TRY(h, rocblas_dtrsm(h->blas, rocblas_side_left, rocblas_fill_upper,
-                            trans ? rocblas_operation_transpose : rocblas_operation_none, rocblas_diagonal_non_unit, m,
-                            (rocblas_int)n, &one, L, (rocblas_int)ldl, X, (rocblas_int)ldx));
+  BLAS_TRY(h, rocblas_dtrsm(h->blas, side, rocblas_fill_upper, trans ? rocblas_operation_transpose : rocblas_operation_none,
+                            rocblas_diagonal_non_unit, r ? (rocblas_int)n : m, r ? m : (rocblas_int)n, &one, L,
+                            (rocblas_int)ldl, X, (rocblas_int)ldx));
   return ISDF_OK;
 }
 }  // namespace
 
-// Large factors are solved block row by block row (LEFT-looking): block jb first receives the contribution of all
-// finished blocks in ONE deep dgemm (the shape rocBLAS runs at the MFMA rate, and it only reads finished rows), then a
-// small dtrsm with the diagonal block.  A monolithic rocBLAS trsm reaches 25-43 TF/s on these shapes, this form ~55-65.
+// Large factors go through the walk with a small dtrsm on each diagonal block: a monolithic rocBLAS trsm reaches 25-43 TF/s
+// on these shapes, this form ~55-65.
 int tri_left(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
   if (h->trsm_substitution) return trsm_lower_left(h, trans, m, n, L, ldl, X, ldx);
   ARG_CHECK(h, L && X && m > 0 && n > 0 && ldl >= m && ldx >= n && n < 2147483647LL && ldx < 2147483647LL && ldl < 2147483647LL);
-  const int NB = trsm_block_size();
-  if (m <= NB) return rb_left(h, trans, m, n, L, ldl, X, ldx);
-  const int nblk = (int)cdiv(m, NB);
-  int rc;
-  if (!trans) {
-    for (int b = 0; b < nblk; ++b) {
-      const int jb = b * NB, nb = std::min(NB, m - jb);
-      if (jb > 0) {   // X[jb:jb+nb] -= L[jb:jb+nb, :jb] X[:jb]
-        rc = gemm_rm(h, 'N', 'N', nb, n, jb, -1.0, L + (int64_t)jb * ldl, ldl, X, ldx, 1.0, X + (int64_t)jb * ldx, ldx);
-        if (rc) return rc;
-      }
-      rc = rb_left(h, false, nb, n, L + (int64_t)jb * ldl + jb, ldl, X + (int64_t)jb * ldx, ldx);
-      if (rc) return rc;
-    }
-  } else {
-    for (int b = nblk - 1; b >= 0; --b) {
-      const int jb = b * NB, nb = std::min(NB, m - jb), j1 = jb + nb;
-      if (j1 < m) {   // X[jb:j1] -= L[j1:, jb:j1]^T X[j1:]
-        rc = gemm_rm(h, 'T', 'N', nb, n, m - j1, -1.0, L + (int64_t)j1 * ldl + jb, ldl, X + (int64_t)j1 * ldx, ldx, 1.0,
-                     X + (int64_t)jb * ldx, ldx);
-        if (rc) return rc;
-      }
-      rc = rb_left(h, true, nb, n, L + (int64_t)jb * ldl + jb, ldl, X + (int64_t)jb * ldx, ldx);
-      if (rc) return rc;
-    }
-  }
-  return ISDF_OK;
+  return blocked_walk(h, false, trans, TRSM_NB, m, n, L, ldl, X, ldx, [&](int bm, const double* Lb, double* Xb) {
+    return rb_trsm(h, rocblas_side_right, trans, bm, n, Lb, ldl, Xb, ldx);
+  });
 }
 
-// X (n x m) <- X op(L)^-1, block column by block column with the same left-looking idea
+// X (n x m) <- X op(L)^-1, block column by block column
 int tri_right(isdf_handle h, bool trans, int m, int64_t n, const double* L, int64_t ldl, double* X, int64_t ldx) {
   if (h->trsm_substitution) return trsm_lower_right(h, trans, m, n, L, ldl, X, ldx);
   ARG_CHECK(h, L && X && m > 0 && n > 0 && ldl >= m && ldx >= m && n < 2147483647LL && ldx < 2147483647LL && ldl < 2147483647LL);
-  const int NB = trsm_block_size();
-  if (m <= NB) return rb_right(h, trans, m, n, L, ldl, X, ldx);
-  const int nblk = (int)cdiv(m, NB);
-  int rc;
-  if (!trans) {
-    // X L^-1: columns from the last block to the first; X[:, jb:j1] -= X[:, j1:] L[j1:, jb:j1]
-    for (int b = nblk - 1; b >= 0; --b) {
-      const int jb = b * NB, nb = std::min(NB, m - jb), j1 = jb + nb;
-      if (j1 < m) {
-        rc = gemm_rm(h, 'N', 'N', n, nb, m - j1, -1.0, X + j1, ldx, L + (int64_t)j1 * ldl + jb, ldl, 1.0, X + jb, ldx);
-        if (rc) return rc;
-      }
-      rc = rb_right(h, false, nb, n, L + (int64_t)jb * ldl + jb, ldl, X + jb, ldx);
-      if (rc) return rc;
-    }
-  } else {
-    // X L^-T: columns from the first block on; X[:, jb:j1] -= X[:, :jb] L[jb:j1, :jb]^T
-    for (int b = 0; b < nblk; ++b) {
-      const int jb = b * NB, nb = std::min(NB, m - jb);
-      if (jb > 0) {
-        rc = gemm_rm(h, 'N', 'T', n, nb, jb, -1.0, X, ldx, L + (int64_t)jb * ldl, ldl, 1.0, X + jb, ldx);
-        if (rc) return rc;
-      }
-      rc = rb_right(h, true, nb, n, L + (int64_t)jb * ldl + jb, ldl, X + jb, ldx);
-      if (rc) return rc;
-    }
-  }
-  return ISDF_OK;
+  return blocked_walk(h, true, trans, TRSM_NB, m, n, L, ldl, X, ldx, [&](int bm, const double* Lb, double* Xb) {
+    return rb_trsm(h, rocblas_side_left, trans, bm, n, Lb, ldl, Xb, ldx);
+  });
 }

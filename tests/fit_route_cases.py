@@ -15,9 +15,9 @@ from test_gpu_fit_solve_sweep import _ints as ints, cdiv
 LIMIT = 2 ** 53
 
 # ---- restatement of the host-side chunking (csrc/fit.hip) -------------------------------------------------------------------
-CPLX_CHUNK = 8192                                   # isdf_fit_apply_cplx, isdf_pair_gram_rows(nh > 0): columns per pass
-TRSM_NB = 1024                                      # trsm_block_size(): rows per block of the left-looking drivers
-SUBST_PANEL, SUBST_BLOCK = 512, 64                  # trsm_lower_left: rows per panel, per substitution block
+CPLX_CHUNK = 8192                                   # pair_rows (isdf_fit_apply_cplx, isdf_pair_gram_rows), nh > 0: columns per pass
+TRSM_NB = 1024                                      # TRSM_NB of trsm.hip: rows per block of blocked_walk under tri_left / tri_right
+SUBST_PANEL, SUBST_BLOCK = 512, 64                  # trsm_lower_left: rows per panel of blocked_walk, per block of the walk inside it
 
 
 def prod_chunk(P):
@@ -35,6 +35,31 @@ def chunks(n, ch):
 def trsm_calls(P, two_sided=False):
     """rocblas_dtrsm calls of one tri_left / tri_right on P rows (default path): one per block of TRSM_NB rows."""
     return cdiv(P, TRSM_NB) * (2 if two_sided else 1)
+
+
+def walk_gemms(m, n, nb, up, inner=None):
+    """(count, summed flop) of the gemm_rm calls of one blocked_walk (csrc/trsm.hip) over m rows with n right-hand sides: blocks
+    of nb from row 0, taken upwards (up: L^-1 X, X L^-T) or downwards (L^-T X, X L^-1); every block but the first taken is
+    updated from all finished rows in one product of 2 (its rows) n (the finished rows) flop.  inner: the block's diagonal solve
+    is itself a walk over blocks of `inner` rows in the same direction (trsm_lower_left)."""
+    count, flop = 0, 0
+    for j0, rows in chunks(m, nb):
+        done = j0 if up else m - (j0 + rows)
+        if done > 0:
+            count, flop = count + 1, flop + 2 * rows * n * done
+        if inner:
+            c, f = walk_gemms(rows, n, inner, up)
+            count, flop = count + c, flop + f
+    return count, flop
+
+
+def solve_gemms(P, n, ups, subst):
+    """rocblas_dgemm[flop] as dict(launches, work) of the walks of one call on a P-row factor, one walk per entry of ups (its
+    direction): tri_left / tri_right on the default path, their substitution twins (a right-sided solve is the left-sided one
+    of the other op on the transpose: same direction, same products) under trsm_substitution."""
+    nb, inner = (SUBST_PANEL, SUBST_BLOCK) if subst else (TRSM_NB, None)
+    walks = [walk_gemms(P, n, nb, up, inner) for up in ups]
+    return dict(launches=sum(c for c, _ in walks), work=float(sum(f for _, f in walks)))
 
 
 # ---- the case lists ---------------------------------------------------------------------------------------------------------

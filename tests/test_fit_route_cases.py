@@ -112,6 +112,54 @@ def test_healthy_matrices_are_exact_integers():
         assert (L0.diagonal() > 0).all()
 
 
+def _enumerate_walk(m, n, sizes, up):
+    """The gemm_rm calls of a walk by direct enumeration: the rows are solved 64, 512 or 1024 at a time (sizes, innermost
+    first: a block of a level never crosses a boundary of the level above, and every level counts from row 0 of its parent);
+    whenever a group of rows at some level starts on rows that the same parent has finished, one product couples the two."""
+    calls = []
+
+    def solve(lo, hi, level):                                  # rows [lo, hi) with everything outside the parent done
+        if level < 0:
+            return
+        nb = sizes[level]
+        starts = list(range(lo, hi, nb))
+        finished = []
+        for j0 in (starts if up else starts[::-1]):
+            rows = list(range(j0, min(hi, j0 + nb)))
+            if finished:
+                calls.append(2 * len(rows) * n * len(finished))
+            solve(rows[0], rows[-1] + 1, level - 1)
+            finished += rows
+    solve(0, m, len(sizes) - 1)
+    return len(calls), sum(calls)
+
+
+def test_walk_gemms_is_the_enumeration_of_the_blocks():
+    """walk_gemms / solve_gemms against the enumeration above on every shape of the solve sweeps, both directions: cdiv(P, 1024)
+    - 1 products per pass on the default path, cdiv(P, 64) - 1 under trsm_substitution (64 divides 512), and the flop of a pass
+    is 2 n times the sum over pairs of blocks of the product of their sizes - the same upwards and downwards."""
+    for P in sorted(set(fc.SOLVE_P + fc.W_P)):
+        for n in fc.SOLVE_N + (P,):
+            for up in (True, False):
+                plain = fc.walk_gemms(P, n, fc.TRSM_NB, up)
+                assert plain == _enumerate_walk(P, n, (fc.TRSM_NB,), up) and plain[0] == fc.cdiv(P, fc.TRSM_NB) - 1
+                sub = fc.walk_gemms(P, n, fc.SUBST_PANEL, up, fc.SUBST_BLOCK)
+                assert sub == _enumerate_walk(P, n, (fc.SUBST_BLOCK, fc.SUBST_PANEL), up)
+                assert sub[0] == fc.cdiv(P, fc.SUBST_BLOCK) - 1
+                sizes = [rows for _, rows in fc.chunks(P, fc.TRSM_NB)]
+                pairs = sum(a * b for i, a in enumerate(sizes) for b in sizes[i + 1:])
+                assert plain[1] == 2 * n * pairs
+            for subst in (0, 1):
+                got = fc.solve_gemms(P, n, (True, False), subst)
+                nb = (fc.SUBST_PANEL, fc.SUBST_BLOCK) if subst else (fc.TRSM_NB, None)
+                both = [fc.walk_gemms(P, n, nb[0], up, nb[1]) for up in (True, False)]
+                assert got == dict(launches=both[0][0] + both[1][0], work=float(both[0][1] + both[1][1]))
+                assert got['work'] < LIMIT
+    assert fc.walk_gemms(2049, 37, fc.TRSM_NB, True) == (2, 2 * 37 * (1024 * 1024 + 2048 * 1))
+    assert fc.walk_gemms(2049, 37, fc.TRSM_NB, False) == (2, 2 * 37 * (1024 * 1 + 1024 * 1025))
+    assert fc.walk_gemms(1024, 37, fc.TRSM_NB, True) == (0, 0) and fc.walk_gemms(65, 1, 512, False, 64) == (1, 2 * 64)
+
+
 def _straddles(values, edge):
     return edge in values and any(v < edge for v in values) and any(v > edge for v in values)
 

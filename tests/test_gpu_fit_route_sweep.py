@@ -79,6 +79,7 @@ from test_gpu_fit_solve_sweep import _bits_equal, _first_diff, _offsets, SUBST
 pytestmark = pytest.mark.gpu
 
 DTRSM = 'rocblas_dtrsm[flop]'
+DGEMM = 'rocblas_dgemm[flop]'
 DPOTRF = 'rocsolver_dpotrf[flop]'
 MUL_ROWS = 'mul_rows_kernel[byte]'
 COMBINE = 'prod_combine_kernel[byte]'
@@ -137,6 +138,15 @@ class _Buf:
 
 def _watched(prof):
     return {k: v['launches'] for k, v in prof.items() if k in WATCHED}
+
+
+def _check_gemms(bad, prof, want):
+    """The updates of the blocked walks: launches and summed flop of rocblas_dgemm against fc.solve_gemms (exact: every product's
+    flop is an integer, the sum far below 2^53)."""
+    ran = prof.get(DGEMM, dict(launches=0, work=0.0))
+    ran = dict(launches=ran['launches'], work=ran['work'])
+    if ran != want:
+        bad.append('%s ran %s, the restatement says %s' % (DGEMM, ran, want))
 
 
 def _check(bad, out, ref, operands, prof=None, want=None):
@@ -420,6 +430,7 @@ def test_factor_solves(be, P, subst):
                 prof = _profiled(be, lambda: _launch_solve(be, entry, d_L.view, X.view))
                 passes = {'solve': (False, True), 'half0': (False,), 'half1': (True,)}[entry]
                 bad = []
+                _check_gemms(bad, prof, fc.solve_gemms(P, n, [not trans for trans in passes], subst))    # L^-1 X walks upwards
                 if subst:
                     want = {SUBST[t]: _subst_launches(P, 1) for t in passes}
                     _check(bad, X, Xt[:, :n], dict(fac=d_L), prof, want)
@@ -468,6 +479,8 @@ def test_W_from_factor_kinds_0_and_2(be, P, subst):
             X = _Buf(be, M, ld=P + 3, out=True)
             prof = _profiled(be, lambda: [be.W_from_factor(d_L.view, k, X.view) for k in kinds])
             bad = []
+            # two walks per kind, both upwards for kind 2 (L^-1 M, then M L^-T) and both downwards for kind 0
+            _check_gemms(bad, prof, fc.solve_gemms(P, P, [k == 2 for k in kinds for _ in range(2)], subst))
             if subst:
                 # a right-sided solve is the left-sided one of the other op on X^T: kind 0 runs L^-T twice, kind 2 L^-1 twice
                 _check(bad, X, Wt, dict(fac=d_L), prof, {SUBST[k == 0]: _subst_launches(P, 2) for k in kinds})

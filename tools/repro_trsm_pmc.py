@@ -1,4 +1,4 @@
-"""Repro for the note in pyscf_isdf_amd/csrc/trsm.hip / include/mi355_isdf.h: rocBLAS dtrsm with a 1.7M-column right-hand side
+"""Repro for the note in DESIGN.md ("The rocprofv3 --pmc abort, root-caused"): rocBLAS dtrsm with a 1.7M-column right-hand side
 (the Cholesky fit route at configs[2]) under `rocprofv3 --pmc`.  Prints the call's exact arguments and rocBLAS's own
 workspace requirement (device-memory size query) first, then runs the solve once through the library and checks it.
 Run plain, and ONCE under the profiler with the interpreter directly after `--`:
@@ -16,7 +16,7 @@ from pyscf_isdf_amd.backend import HipBackend
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 1728000
 be = HipBackend(0)
-print('rb_left(m=%d, n=%d): rocblas_dtrsm(side=right, uplo=upper, transA=none, diag=non_unit, M=%d, N=%d, lda=%d, ldb=%d); '
+print('rb_trsm(m=%d, n=%d): rocblas_dtrsm(side=right, uplo=upper, transA=none, diag=non_unit, M=%d, N=%d, lda=%d, ldb=%d); '
       'M*N = %d elements (int32 max 2147483647), B = %.1f GiB' % (m, n, n, m, m, n, m * n, 8.0 * m * n / 2 ** 30), flush=True)
 # rocBLAS's own statement of the workspace this call needs
 rb = ctypes.CDLL('librocblas.so', mode=ctypes.RTLD_GLOBAL)
