@@ -714,6 +714,23 @@ int isdf_thc_pair(isdf_handle h, int P, const double* d_Xo, int64_t ldo, int no,
                   int nv, const double* d_sv, double* d_A, int64_t lda);
 int isdf_trace_sq(isdf_handle h, int n, const double* d_B, int64_t ldb, double* result);
 
+/* Direct RPA correlation energy from the same factors (host loop in pyscf_isdf_amd/thc_rpa.py): per frequency
+ * ln det(1 + W S) - Tr(W S), S = -chi0(i omega) in the point basis; W S by isdf_gemm_nt (S is symmetric to the bit), Tr(W S) by
+ * isdf_dot, the second-order term Tr[(W S)^2] by isdf_trace_sq.
+ *   isdf_thc_chi0:  S (P, lds) <- sum_ia Xo[p,i] Xv[p,a] D[i,a] Xo[q,i] Xv[q,a]; Xo (P, ldo), Xv (P, ldv), D (no, ldd) row-major,
+ *                   ldo >= no, ldv >= nv, ldd >= nv, lds >= P (else ISDF_ERR_ARG).  One launch: the tile, unit decode and store of
+ *                   isdf_thc_pair with one set of v_mfma_f64_16x16x4_f64 accumulators; the K dimension is the pair index (i, a),
+ *                   whose operand rows Xo[p,i] Xv[p,a] are formed at the fragment read and never stored (D multiplies one side).
+ *                   K tails are zero-filled.  Only the lower triangle is computed and every value is stored at (p, q) and (q, p):
+ *                   the same bits.  Any leading dimensions and alignment (16-byte aligned rows of Xo and Xv take the vector
+ *                   loads); columns >= P of S are not touched
+ *   isdf_logdet_lu: A (n, lda) <- the LU factors of A + shift I (rocsolver_dgetrf); *logabs (host) = ln|det(A + shift I)|, *sign
+ *                   (host) = its sign (+1 or -1) from the negative pivots and the row swaps, summed by one workgroup in a fixed
+ *                   order; a singular matrix gives ISDF_ERR_NUM; synchronises */
+int isdf_thc_chi0(isdf_handle h, int P, const double* d_Xo, int64_t ldo, int no, const double* d_Xv, int64_t ldv, int nv,
+                  const double* d_D, int64_t ldd, double* d_S, int64_t lds);
+int isdf_logdet_lu(isdf_handle h, int n, double* d_A, int64_t lda, double shift, double* logabs, int* sign);
+
 /* Dense helper behind S5/S6 (exposed for tests and micro-benchmarks):
  *   C (M, ldc) = alpha * A (M, lda) * (B (N, ldb) .* kscale[None, :])^T + beta * C,
  * K contiguous in both operands (the W = V Theta^T / vj = ao (v.ao)^T shape); d_kscale may be NULL.

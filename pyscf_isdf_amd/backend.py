@@ -607,6 +607,28 @@ class HipBackend:
         self.handle.call('isdf_trace_sq', n, self._p(B), B.stride(0), ctypes.byref(out))
         return out.value
 
+    # ---- direct RPA from the same factors (thc_rpa.py) ---------------------------------------------------
+    def thc_chi0(self, Xo, Xv, D, S):
+        """S (P, P) <- sum_ia Xo[:, i] Xv[:, a] D[i, a] (Xo[:, i] Xv[:, a])^T in one launch, symmetric to the bit; Xo (P, no),
+        Xv (P, nv), D (no, nv) with the last index contiguous (include/mi355_isdf.h isdf_thc_chi0)."""
+        self._stream()
+        P, no = Xo.shape
+        nv = Xv.shape[1]
+        assert Xv.shape[0] == P and tuple(S.shape) == (P, P) and tuple(D.shape) == (no, nv)
+        assert Xo.stride(1) == 1 and Xv.stride(1) == 1 and S.stride(1) == 1 and D.stride(1) == 1
+        self.handle.call('isdf_thc_chi0', P, self._p(Xo), Xo.stride(0), no, self._p(Xv), Xv.stride(0), nv, self._p(D), D.stride(0),
+                         self._p(S), S.stride(0))
+
+    def logdet_lu(self, A, shift=0.0):
+        """(ln|det(A + shift I)|, sign) of a square A, which is overwritten by the LU factors (include/mi355_isdf.h isdf_logdet_lu);
+        synchronises."""
+        self._stream()
+        n = A.shape[0]
+        assert tuple(A.shape) == (n, n) and A.stride(1) == 1
+        logabs, sign = ctypes.c_double(0.0), ctypes.c_int(0)
+        self.handle.call('isdf_logdet_lu', n, self._p(A), A.stride(0), float(shift), ctypes.byref(logabs), ctypes.byref(sign))
+        return logabs.value, sign.value
+
     # ---- k-point M^q from the packed half spectra of the fit rows (DESIGN.md section 6b) ------------------------------------
     def pack_table_pm(self, table, mesh, idx, scale, s, a):
         """s, a (ldx,) <- scale (c(G_t) +- (m_t - 1) c(-G_t)) on the packed points idx (int32 half-spectrum indices), each value on

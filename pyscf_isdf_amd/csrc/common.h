@@ -58,7 +58,7 @@ struct isdf_ctx {
   // pair-density rows aoP ao: 0 = rocBLAS dgemm (default: 74 TF/s on that shape), 1 = the own MFMA NN kernel of gemm_f64.hip with
   // the square fused into its epilogue (66-71 TF/s; kept as the library-free route and for A/B runs)
   int gemm_nn_own = 0;
-  int attr_gemm_b = 0, attr_gemm_nn = 0, attr_gemm_nn_had = 0, attr_gram_tri = 0, attr_herm = 0, attr_thc_pair = 0;   // dynamic-LDS attributes raised on this handle's device
+  int attr_gemm_b = 0, attr_gemm_nn = 0, attr_gemm_nn_had = 0, attr_gram_tri = 0, attr_herm = 0, attr_thc_pair = 0, attr_thc_chi0 = 0;   // dynamic-LDS attributes raised on this handle's device
   // per-atom candidate selection: 1 = form the blocks' Gram triangles once on the matrix cores when the caller passes a
   // workspace (default), 0 = always stream the AO slab at every pivot (select_ip.hip)
   int cand_gram = 1;

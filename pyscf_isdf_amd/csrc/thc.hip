@@ -14,6 +14,12 @@
 //    Algorithmic work: P (P + 1) (no + nv) flop (the lower triangle: the mirrored half is stores only); bound: FP64 MFMA.
 //  * trace_sq: sum_ij B_ij B_ji.  32 x 32 tile pairs (ti >= tj): the tile (tj, ti) goes through LDS so that both reads are
 //    coalesced; an off-diagonal pair counts twice.  One partial per workgroup, summed by a second kernel in a fixed order.
+// Direct RPA from the same factors (host orchestration in pyscf_isdf_amd/thc_rpa.py): per frequency
+// ln det(1 + W S) - Tr(W S) with S_PQ = sum_ia Y_P,ia d_ia Y_Q,ia, Y_P,ia = Xo_Pi Xv_Pa.
+//  * thc_chi0_kernel: S in one launch with thc_pair_kernel's tile, wave grid, unit decode, triangle rule and mirrored store, one
+//    accumulator set.  The K dimension is the pair index (i, a); the rows of Y are formed at the fragment read (one v_mul_f64 per
+//    A fragment, two per B fragment, which carries d) and never stored.
+//  * logdet_diag_kernel: sum ln|u_ii|, the count of negative u_ii and of row swaps behind rocsolver_dgetrf, in a fixed order.
 #include "common.h"
 #include "gemm_tile.h"
 #include <cmath>
@@ -140,6 +146,188 @@ __global__ __launch_bounds__(PTPB, 2) void thc_pair_kernel(PairArgs g) {
   })
 }
 
+// ---- direct RPA: S(w) = Y diag(d) Y^T over the pair index, Y never stored --------------------------------------------------------------
+struct Chi0Args {
+  const double* Xo; int64_t ldo; int no;
+  const double* Xv; int64_t ldv; int nv;
+  const double* D; int64_t ldd;
+  double* S; int64_t lds;
+  int P;
+  int64_t nunits, nunits_pad;
+};
+
+// four values of a row from column k on, zero past K; FAST: the quad is 16-byte aligned
+template <bool FAST>
+__device__ __forceinline__ void load_quad(const double* __restrict__ q, int k, int K, double (&v)[4]) {
+  if (k + 3 < K) {
+    if (FAST) {
+      const double2 u0 = *reinterpret_cast<const double2*>(q), u1 = *reinterpret_cast<const double2*>(q + 2);
+      v[0] = u0.x; v[1] = u0.y; v[2] = u1.x; v[3] = u1.y;
+    } else {
+      v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    }
+  } else {
+    v[0] = (k < K) ? q[0] : 0.0;
+    v[1] = (k + 1 < K) ? q[1] : 0.0;
+    v[2] = (k + 2 < K) ? q[2] : 0.0;
+    v[3] = 0.0;
+  }
+}
+
+__device__ __forceinline__ void store_quad(double* q, const double (&v)[4]) { q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3]; }
+
+// A chunk is 16 occupied x 16 virtual pair columns: the 16-deep Xv chunk and the 16-wide Xo block of both tile rows and the
+// 16 x 16 block of d are staged global -> registers (during the previous chunk's products) -> LDS.  Per chunk a wave reads its Xv
+// fragments once and walks the occupied index: a = Xv Xo[., i], b = Xv (Xo[., i] d[i, .]), 4 K-steps of 8 MFMA each.  The Xo
+// block is restaged only when the occupied block changes (the virtual chunk is the fast index).
+// smem: Xv tm | Xv tn | Xo tm | Xo tn (PT * PLD each) | d (16 x 16)
+template <bool FAST>
+__global__ __launch_bounds__(PTPB, 2) void thc_chi0_kernel(Chi0Args g) {
+  extern __shared__ double smem[];
+  const int64_t unit = xcd_unit(g.nunits_pad);
+  if (unit >= g.nunits) return;
+  int tm, tn;
+  decode_tri(unit, tm, tn);
+  double* sVa = smem;
+  double* sVb = sVa + PT * PLD;
+  double* sOa = sVb + PT * PLD;
+  double* sOb = sOa + PT * PLD;
+  double* sD = sOb + PT * PLD;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int srow = tid >> 2, sseg = tid & 3;            // staging: row srow of both tiles, column offset 4 sseg .. + 3
+  const int64_t ra = min(tm * PT + srow, g.P - 1), rb = min(tn * PT + srow, g.P - 1);
+  const double* pva = g.Xv + ra * g.ldv + 4 * sseg;
+  const double* pvb = g.Xv + rb * g.ldv + 4 * sseg;
+  const double* poa = g.Xo + ra * g.ldo + 4 * sseg;
+  const double* pob = g.Xo + rb * g.ldo + 4 * sseg;
+  const int di = tid >> 4, da = tid & 15;               // staging of d: threads 0 .. 255, entry (di, da) of the block
+  const int nvc = (g.nv + PK - 1) / PK, noc = (g.no + PK - 1) / PK;
+  d4 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+  const int frow = lane & 15, fk = lane >> 4;
+  const int aoff = (wm * 64 + frow) * PLD, boff = (wn * 32 + frow) * PLD;
+  double va[4], vb[4], oa[4], ob[4], dd = 0.0;
+#define ISDF_CHI0_LOAD(OB, VC)                                                                \
+  {                                                                                           \
+    const int k = (VC) * PK + 4 * sseg;                                                       \
+    load_quad<FAST>(pva + (VC) * PK, k, g.nv, va);                                            \
+    load_quad<FAST>(pvb + (VC) * PK, k, g.nv, vb);                                            \
+    if ((VC) == 0) {                                                                          \
+      const int i0 = (OB) * PK + 4 * sseg;                                                    \
+      load_quad<FAST>(poa + (OB) * PK, i0, g.no, oa);                                         \
+      load_quad<FAST>(pob + (OB) * PK, i0, g.no, ob);                                         \
+    }                                                                                         \
+    if (tid < 256) {                                                                          \
+      const int i = (OB) * PK + di, a = (VC) * PK + da;                                       \
+      dd = (i < g.no && a < g.nv) ? g.D[(int64_t)i * g.ldd + a] : 0.0;                        \
+    }                                                                                         \
+  }
+#define ISDF_CHI0_STORE(VC)                                                                   \
+  {                                                                                           \
+    store_quad(sVa + srow * PLD + 4 * sseg, va);                                              \
+    store_quad(sVb + srow * PLD + 4 * sseg, vb);                                              \
+    if ((VC) == 0) {                                                                          \
+      store_quad(sOa + srow * PLD + 4 * sseg, oa);                                            \
+      store_quad(sOb + srow * PLD + 4 * sseg, ob);                                            \
+    }                                                                                         \
+    if (tid < 256) sD[tid] = dd;                                                              \
+  }
+  ISDF_CHI0_LOAD(0, 0)
+  ISDF_CHI0_STORE(0)
+  __syncthreads();
+  for (int ob_ = 0; ob_ < noc; ++ob_) {
+    const int ilen = min(PK, g.no - ob_ * PK);
+    for (int vc = 0; vc < nvc; ++vc) {
+      const int klen = min(PK, g.nv - vc * PK);
+      int nob = ob_, nvc_ = vc + 1;                     // the next chunk
+      if (nvc_ == nvc) { nvc_ = 0; ++nob; }
+      const bool more = nob < noc;
+      if (more) ISDF_CHI0_LOAD(nob, nvc_)
+      double av[4][4], bv[4][2];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[kk][i] = sVa[aoff + i * 16 * PLD + kk * 4 + fk];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bv[kk][j] = sVb[boff + j * 16 * PLD + kk * 4 + fk];
+      }
+      for (int io = 0; io < ilen; ++io) {
+        double xa[4], xb[2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xa[i] = sOa[aoff + i * 16 * PLD + io];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) xb[j] = sOb[boff + j * 16 * PLD + io];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          if (kk * 4 < klen) {
+            const double dk = sD[io * PK + kk * 4 + fk];
+            double af[4], bf[2];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = av[kk][i] * xa[i];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = bv[kk][j] * (xb[j] * dk);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+              for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();                                  // every wave has read this chunk
+      if (more) ISDF_CHI0_STORE(nvc_)
+      __syncthreads();
+    }
+  }
+#undef ISDF_CHI0_LOAD
+#undef ISDF_CHI0_STORE
+  const bool diag = tm == tn;
+  ISDF_STORE_ACC(4, 2, tm * PT + wm * 64, tn * PT + wn * 32, g.P, g.P, {
+    if (!(diag && col > row)) {
+      const double v = acc[i][j][r];
+      g.S[(int64_t)row * g.lds + col] = v;
+      if (row != col) g.S[(int64_t)col * g.lds + row] = v;
+    }
+  })
+}
+
+// ---- ln|det| from the LU factors ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_unit_diag_kernel(double* __restrict__ A, int64_t lda, int n, double shift) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) A[(int64_t)i * lda + i] += shift;
+}
+
+// out[0] = sum_i ln|u_ii|; out[1] = number of negative u_ii + number of row swaps (ipiv[i] != i + 1); out[2] = number of zero or
+// non-finite u_ii.  One workgroup: thread t takes i = t, t + 256, ... in order, then the tree: a fixed order.
+__global__ __launch_bounds__(256) void logdet_diag_kernel(const double* __restrict__ A, int64_t lda, int n, const int* __restrict__ ipiv,
+                                                          double* __restrict__ out) {
+  __shared__ double sh[256];
+  __shared__ int sn[256], sz[256];
+  double s = 0.0;
+  int neg = 0, zero = 0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double u = A[(int64_t)i * lda + i];
+    if (!(fabs(u) > 0.0) || !isfinite(u)) { ++zero; continue; }
+    s += log(fabs(u));
+    neg += (u < 0.0) + (ipiv[i] != i + 1);
+  }
+  sh[threadIdx.x] = s; sn[threadIdx.x] = neg; sz[threadIdx.x] = zero;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      sh[threadIdx.x] += sh[threadIdx.x + w];
+      sn[threadIdx.x] += sn[threadIdx.x + w];
+      sz[threadIdx.x] += sz[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = sh[0]; out[1] = (double)sn[0]; out[2] = (double)sz[0]; }
+}
+
 // ---- trace of the square -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void trace_sq_partial_kernel(const double* __restrict__ B, int64_t ldb, int n,
                                                                double* __restrict__ partial) {
@@ -209,6 +397,64 @@ extern "C" int isdf_thc_pair(isdf_handle h, int P, const double* d_Xo, int64_t l
   else
     hipLaunchKernelGGL(thc_pair_kernel<false>, dim3((unsigned)g.nunits_pad), dim3(PTPB), lds, h->stream, g);
   KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_thc_chi0(isdf_handle h, int P, const double* d_Xo, int64_t ldo, int no, const double* d_Xv, int64_t ldv, int nv,
+                             const double* d_D, int64_t ldd, double* d_S, int64_t lds) {
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, P > 0 && no > 0 && nv > 0 && d_Xo && d_Xv && d_D && d_S);
+  ARG_CHECK(h, ldo >= no && ldv >= nv && ldd >= nv && lds >= P);
+  Chi0Args g;
+  g.Xo = d_Xo; g.ldo = ldo; g.no = no;
+  g.Xv = d_Xv; g.ldv = ldv; g.nv = nv;
+  g.D = d_D; g.ldd = ldd;
+  g.S = d_S; g.lds = lds; g.P = P;
+  const int64_t nt = cdiv(P, PT);
+  g.nunits = nt * (nt + 1) / 2;
+  g.nunits_pad = cdiv(g.nunits, 8) * 8;
+  const size_t smem = sizeof(double) * (4 * PT * PLD + PK * PK);
+  if (!h->attr_thc_chi0) {
+    HIP_TRY(h, hipFuncSetAttribute((const void*)thc_chi0_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    HIP_TRY(h, hipFuncSetAttribute((const void*)thc_chi0_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    h->attr_thc_chi0 = 1;
+  }
+  ProfScope ps(h, "thc_chi0_kernel[flop]", (double)P * ((double)P + 1.0) * (double)no * (double)nv);   // the lower triangle
+  if (rows16(d_Xo, ldo) && rows16(d_Xv, ldv))
+    hipLaunchKernelGGL(thc_chi0_kernel<true>, dim3((unsigned)g.nunits_pad), dim3(PTPB), smem, h->stream, g);
+  else
+    hipLaunchKernelGGL(thc_chi0_kernel<false>, dim3((unsigned)g.nunits_pad), dim3(PTPB), smem, h->stream, g);
+  KERNEL_CHECK(h);
+  return ISDF_OK;
+}
+
+extern "C" int isdf_logdet_lu(isdf_handle h, int n, double* d_A, int64_t lda, double shift, double* logabs, int* sign) {
+  // A <- the LU factors of A + shift I (rocsolver_dgetrf on the column-major view, which is A^T: the same determinant);
+  // *logabs = ln|det|, *sign = +-1; synchronises the work stream
+  if (!h) return ISDF_ERR_ARG;
+  ARG_CHECK(h, n > 0 && d_A && logabs && sign && lda >= n && lda < 2147483647LL);
+  int* info = (int*)isdf_ws(h, "logdet_lu", 64 + sizeof(int) * (size_t)n);
+  if (!info) return ISDF_ERR_HIP;
+  double* out = (double*)(info + 2);                    // 8-byte aligned: the workspace is
+  int* ipiv = info + 16;
+  if (shift != 0.0) {
+    hipLaunchKernelGGL(add_unit_diag_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream, d_A, lda, n, shift);
+    KERNEL_CHECK(h);
+  }
+  {
+    ProfScope ps(h, "rocsolver_dgetrf[flop]", 2.0 * (double)n * n * n / 3.0);
+    BLAS_TRY(h, rocsolver_dgetrf(h->blas, n, n, d_A, (rocblas_int)lda, ipiv, info));
+  }
+  hipLaunchKernelGGL(logdet_diag_kernel, dim3(1), dim3(256), 0, h->stream, d_A, lda, n, ipiv, out);
+  KERNEL_CHECK(h);
+  struct { int info, pad; double out[3]; } host;
+  HIP_TRY(h, hipMemcpyAsync(&host, info, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (host.info != 0 || host.out[2] != 0.0)
+    return isdf_fail(h, ISDF_ERR_NUM, "isdf_logdet_lu: the matrix is singular (dgetrf status %d, %d zero or non-finite pivots)", host.info,
+                     (int)host.out[2]);
+  *logabs = host.out[0];
+  *sign = (((int64_t)host.out[1]) & 1) ? -1 : 1;
   return ISDF_OK;
 }
 

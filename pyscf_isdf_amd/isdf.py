@@ -1158,4 +1158,11 @@ class ISDF(FitRouteMixin, ShardedMixin, KPointMixin, HcoreMixin, EriSurfaceMixin
         from .thc_mp2 import mp2_os
         return mp2_os(self, mo_coeff, mo_energy, mo_occ, rtol=rtol, c_os=c_os)
 
+    def rpa(self, mo_coeff, mo_energy, mo_occ, nw=40, x0=0.5):
+        """Direct RPA correlation energy from the THC form of the factors on the device, per imaginary frequency one pair-index
+        product, one P^3 product and one LU: thc_rpa.rpa (DESIGN.md section 8c).  Closed shell, Gamma point, pair_space='ao';
+        everything else raises before any work."""
+        from .thc_rpa import rpa
+        return rpa(self, mo_coeff, mo_energy, mo_occ, nw=nw, x0=x0)
+
 

@@ -135,6 +135,8 @@ SIGNATURES = {
     'isdf_herm_kscale_nt': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_dbl, c_vp, c_vp, c_i64]),
     'isdf_thc_pair': (c_int, [c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64]),
     'isdf_trace_sq': (c_int, [c_vp, c_int, c_vp, c_i64, c_vp]),
+    'isdf_thc_chi0': (c_int, [c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64]),
+    'isdf_logdet_lu': (c_int, [c_vp, c_int, c_vp, c_i64, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_int)]),
     'isdf_get_k_exact': (c_int, [c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     'isdf_get_k': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp]),
 }

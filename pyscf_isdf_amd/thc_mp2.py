@@ -56,9 +56,9 @@ class ThcMP2Result:
         return 'ThcMP2Result(e_os=%.12g, e_sos=%.12g, ngrid=%d, rtol=%g)' % (self.e_os, self.e_sos, self.ngrid, self.rtol)
 
 
-def _refuse(df, mo_energy, mo_occ):
-    """Everything mp2_os does not do, before any work: no build, no buffer, no change of the object."""
-    what = 'mp2_os'
+def _refuse(df, mo_energy, mo_occ, what='mp2_os'):
+    """Everything mp2_os (and thc_rpa.rpa, which passes its own name) does not do, before any work: no build, no buffer, no change
+    of the object."""
     if df.kpts_symm is not None:
         raise NotImplementedError('%s with k-point symmetry is not implemented (Gamma point only)' % what)
     if not df._is_gamma(df.kpts) or not df._is_gamma(df.kpts_band):

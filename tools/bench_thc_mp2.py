@@ -16,9 +16,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyscf_isdf_amd import workloads
 from pyscf_isdf_amd.isdf import ISDF
 
-print('device', torch.cuda.get_device_name(0), 'CUs', torch.cuda.get_device_properties(0).multi_processor_count, flush=True)
-print('a new capability: there is no parent-commit time to compare with', flush=True)
-args = sys.argv[1:] or ['diamond-222-dzvp-80:10:scf', 'diamond-444-dzvp-120:12:random']
 
 
 def wall(fn):
@@ -110,6 +107,9 @@ def run(name, c_isdf, orbitals):
     torch.cuda.empty_cache()
 
 
-for arg in args:
-    parts = arg.split(':')
-    run(parts[0], int(parts[1]) if len(parts) > 1 else 10, parts[2] if len(parts) > 2 else 'scf')
+if __name__ == '__main__':          # tools/bench_thc_rpa.py imports the orbitals from here
+    print('device', torch.cuda.get_device_name(0), 'CUs', torch.cuda.get_device_properties(0).multi_processor_count, flush=True)
+    print('a new capability: there is no parent-commit time to compare with', flush=True)
+    for arg in sys.argv[1:] or ['diamond-222-dzvp-80:10:scf', 'diamond-444-dzvp-120:12:random']:
+        parts = arg.split(':')
+        run(parts[0], int(parts[1]) if len(parts) > 1 else 10, parts[2] if len(parts) > 2 else 'scf')
